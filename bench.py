@@ -1,9 +1,20 @@
 #!/usr/bin/env python
 """bench.py -- candidate-evals/sec of the ES evaluate-population hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ..., one rank
     per GPU, or from a bare shell: without WORLD_SIZE in the environment bench.py launches those N ranks itself)
+
+A plain run sets up, warms up (W steps), times K steps, writes the last timed step's outputs if --dump-outputs is given, and
+prints the JSON line.  --full adds everything the headline figure does not need, behind the timed region: the eager,
+event-timed steps and the conv / DSP rooflines (left out by --no-roofline), the second timed region at pop 512 (--no-pop512)
+and the CPU baseline (--no-cpu-baseline).
+
+--dump-outputs DIR writes what the last timed step handed its caller, from rank 0, as DIR/<name>.npy: fitness (float64, the
+gathered fitness vector tell() received), population (float64, the parameter rows ask() returned), embeds_mid / embeds_side
+(float32, this rank's AFx-Rep embeddings) and best_x (float64, the CMA-ES best candidate after that tell()).  Inputs are seeded:
+the same arguments give the same inputs on every run.  Above 64 MB in all, a fixed seeded sample of rows is written per
+array, with its row indices in <name>_rows.npy.
 
 One step = one ES iteration on synthetic input: ask() -> render the population through the
 effect chain -> log-mel -> AFx-Rep (Cnn14) -> cosine loss -> [all-gather fitness] -> tell().
@@ -12,7 +23,7 @@ EQ/comp/reverb/EQ/gain (D = 45), AFx-Rep metric with seeded random weights (the 
 not available offline).  For N > 1 every GPU evaluates its own 256 candidates of a 256*N
 population (weak scaling, configs[3] shape) and the fitness scalars are all-gathered over RCCL.
 
-The JSON line also carries
+The JSON line also carries (roofline, roofline_dsp, launch_mode.eager_ms_per_step, north_star_pop512 and cpu_baseline with --full only)
   roofline     : one object per conv KERNEL FAMILY, never mixed: "f32" = the exact-f32 MFMA layers (peak 157.3 TFLOP/s),
                  "f16-stream" = the split-precision streaming convolutions (f16 hi + lo operands, peak 2 500 TFLOP/s dense,
                  bound by filling LDS: `bound` says so and `lds_fill` carries bytes copied into LDS / time against the L2 -> LDS
@@ -340,6 +351,27 @@ def workload_string(args, cfg, world, D, kinds):
             "CMA-ES seed 42")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: name -> float32 / float64 ndarray, written as out_dir/<name>.npy.  Above `limit` bytes in all, every array larger
+    than limit / 16 keeps the same share of its rows, chosen by a fixed seed, and their indices go to <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    big = {name for name, a in arrays.items() if a.nbytes > limit // 16 and a.ndim >= 1 and a.shape[0] > 1}
+    small_bytes = sum(a.nbytes for name, a in arrays.items() if name not in big)
+    big_bytes = sum(arrays[name].nbytes for name in big)
+    # 10 % headroom for the index files and the .npy headers
+    share = 1.0 if small_bytes + big_bytes <= limit else 0.9 * (limit - small_bytes) / big_bytes
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if share < 1.0 and name in big:
+            rows = np.sort(np.random.default_rng(2025).choice(a.shape[0], max(1, int(a.shape[0] * share)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -350,12 +382,21 @@ def main():
                          "configurations (their per-GPU share at any --gpus)")
     ap.add_argument("--pop-per-gpu", type=int, default=None)
     ap.add_argument("--seconds", type=float, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-pop512", action="store_true", help="skip the second timed region at BASELINE.json's target population (512 per GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the eager, event-timed steps and the rooflines")
+    ap.add_argument("--no-pop512", action="store_true", help="with --full: skip the second timed region at BASELINE.json's target population (512 per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the rooflines, the pop-512 region and the CPU baseline (off: a plain run measures "
+                         "only the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_pop512 = True
     cfg = BASELINE_CONFIGS[args.config]
     args.steps = cfg["steps"] if args.steps is None else args.steps
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.pop_per_gpu = cfg["pop_per_gpu"] if args.pop_per_gpu is None else args.pop_per_gpu
     args.seconds = cfg["seconds"] if args.seconds is None else args.seconds
 
@@ -452,13 +493,15 @@ def main():
     es = cmaes.CMAEvolutionStrategy(np.ones(D) * 0.5, 0.33, {"bounds": [0, 1], "popsize": P_total, "seed": 42})
 
     last_f = []   # fitness vector of the last step (its hash goes into the line: equal runs are comparable bit for bit)
+    last_out = {}  # what the last step handed back (population, embeddings): read by --dump-outputs after the timed region
     stage_s = [0.0, 0.0, 0.0]  # evaluate (ask + launches + the sync that ends them), gather, tell -- host clocks of this rank
 
     def step():
         t_a = time.perf_counter()
         W = es.ask()
         lo, hi = shard_bounds(P_total, rank, world)
-        loss, _, _ = ev.evaluate(W[lo:hi])
+        loss, embeds, _ = ev.evaluate(W[lo:hi])
+        last_out["W"], last_out["embeds"] = W, embeds
         es.prefetch()  # the next generation's normal deviates, drawn while the GPU works (as run_es does)
         if world > 1:
             torch.cuda.synchronize()   # N > 1 only: separates this rank's own work from its wait for the slowest rank
@@ -489,6 +532,12 @@ def main():
     stages_ms = [1e3 * v / args.steps for v in stage_s]
     import hashlib
     fitness_sha = hashlib.sha256(np.asarray(last_f, dtype=np.float64).tobytes()).hexdigest()[:16]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "fitness": np.asarray(last_f, dtype=np.float64),
+            "population": np.asarray(last_out["W"], dtype=np.float64),
+            **{f"embeds_{k}": (v if v.dtype == torch.float64 else v.float()).cpu().numpy() for k, v in last_out["embeds"].items()},
+            "best_x": np.asarray(es.best_x, dtype=np.float64)})
     conv_each, conv_launches = (ctypes.c_double * 65536)(), ctypes.c_int(0)
     graph_replay = bool(ev._graphs)   # the timed steps replayed the evaluate step's hipGraph (the product default)
     eager_region = not args.no_roofline   # EVERY rank runs it (its steps contain the fitness collective); rank 0 records the events
@@ -580,7 +629,7 @@ def main():
     out["launch_mode"] = {"timed_region": "one hipGraph replay per evaluate step (render -> log-mel -> Cnn14 -> loss)" if graph_replay else "eager launches",
                           "eager_ms_per_step": round(dt_eager / args.steps * 1e3, 3) if (timing and graph_replay) else None,
                           "note": "per-launch conv durations (roofline) are HIP events around the eager launches of the same steps, repeated right "
-                                  "behind the timed region" if graph_replay else None}
+                                  "behind the timed region" if (graph_replay and eager_region) else None}
     if pop512 is not None:
         out["north_star_pop512"] = pop512
     if rank == 0:

@@ -723,7 +723,7 @@ def test_bench_gpus2_self_launches_its_ranks(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["STITO_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--seconds", "2",
-                          "--pop-per-gpu", "8", "--no-cpu-baseline", "--no-pop512"], env=env, capture_output=True, text=True, timeout=900)
+                          "--pop-per-gpu", "8", "--full", "--no-cpu-baseline", "--no-pop512"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -755,6 +755,38 @@ def test_bench_config_switch_runs_the_8gpu_configurations_at_one_gpu(dev):
         assert d["value"] > 0 and d["n_gpus"] == 1 and d["config"]["baseline_config"] == cfg and word in d["config"]["workload"]
         assert f"(D={D})" in d["config"]["workload"] and ("NoiseShapedReverb(96000 taps)" in d["config"]["chain"]) == (cfg == 4)
         assert "north_star_pop512" not in d and d["vs_baseline"] is None
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(dev, tmp_path):
+    """A plain `bench.py` run (no --full) times --steps steps and measures nothing else; --dump-outputs writes what the last
+    timed step handed its caller.  Two runs with the same arguments write the same arrays, and the dumped fitness is the vector
+    whose hash the line carries."""
+    import hashlib
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--seconds", "2",
+                              "--pop-per-gpu", "12", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        line = json.loads(js[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+        assert abs(line["value"] - 12 * 3 / (line["ms_per_step"] * 3 / 1e3)) < 1e-2 * line["value"]
+        for k in ("roofline", "roofline_dsp", "north_star_pop512", "cpu_baseline"):
+            assert k not in line, k
+        assert line["launch_mode"]["eager_ms_per_step"] is None
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrs) == {"fitness", "population", "embeds_mid", "embeds_side", "best_x"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["fitness"].shape == (12,) and arrs["population"].shape == (12, 45) and arrs["embeds_mid"].shape[0] == 12
+        assert hashlib.sha256(arrs["fitness"].tobytes()).hexdigest()[:16] == line["last_fitness_sha16"]
+        assert np.isfinite(arrs["fitness"]).all() and np.isfinite(arrs["embeds_side"]).all()
+        dumps.append(arrs)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
 
 
 def test_one_rank_rccl_group_runs_the_collective_branch(dev):

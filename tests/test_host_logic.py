@@ -496,6 +496,33 @@ def test_bench_measurement_bookkeeping(tmp_path, monkeypatch):
     assert t is None and "was taken on kernel sources" in note
 
 
+def test_bench_dump_outputs_stays_within_its_limit(tmp_path):
+    """bench.py --dump-outputs: arrays under the limit are written whole; above it the large ones are cut to a fixed, seeded
+    sample of rows (indices beside them), the small ones stay whole, every file is float32 / float64 and the directory
+    stays under the limit."""
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"fitness": rng.random(300), "population": rng.random((300, 45)), "embeds_mid": rng.random((300, 512)).astype(np.float32)}
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), arrays)
+    assert sorted(os.listdir(whole)) == ["embeds_mid.npy", "fitness.npy", "population.npy"]
+    for k, a in arrays.items():
+        np.testing.assert_array_equal(np.load(whole / f"{k}.npy"), a)
+    limit = 300 * 512 * 4 // 2
+    cut = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), arrays, limit=limit)
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= limit
+        np.testing.assert_array_equal(np.load(d / "fitness.npy"), arrays["fitness"])
+        rows = np.load(d / "embeds_mid_rows.npy")
+        assert rows.dtype == np.float64 and 0 < len(rows) < 300 and np.all(np.diff(rows) > 0)
+        np.testing.assert_array_equal(np.load(d / "embeds_mid.npy"), arrays["embeds_mid"][rows.astype(np.int64)])
+        assert all(np.load(d / f).dtype in (np.float32, np.float64) for f in os.listdir(d))
+        cut.append(rows)
+    np.testing.assert_array_equal(cut[0], cut[1])
+
+
 def test_bench_self_launches_ranks_dryrun():
     """bench.py started from a bare shell with --gpus 2 and no WORLD_SIZE launches its own ranks through
     torch.distributed.run.  STITO_BENCH_DRYRUN=1 stops each rank after the gloo rendezvous + the

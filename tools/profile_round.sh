@@ -17,10 +17,10 @@ STITO_GRAPH=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -- $BENC
 (cd $R && python profiles/summarize_pmc_bench.py gpurun_out/r6p/pmc_fetch/*/*_results.db gpurun_out/r6p/pmc_write/*/*_results.db 512 gpurun_out/r6p/conv_pmc_traffic.json > gpurun_out/r6p/conv_pmc_traffic.txt 2>&1 && cp gpurun_out/r6p/conv_pmc_traffic.json profiles/round6_conv_pmc_traffic.json)
 (cd $R && python profiles/summarize_pmc_dsp.py gpurun_out/r6p/pmc_fetch/*/*_results.db gpurun_out/r6p/pmc_write/*/*_results.db 256 480000 gpurun_out/r6p/dsp_pmc_traffic.json > gpurun_out/r6p/dsp_pmc_traffic.txt 2>&1 && cp gpurun_out/r6p/dsp_pmc_traffic.json profiles/round6_dsp_pmc_traffic.json)
 cat $O/conv_pmc_traffic.txt | cut -c1-60,92-170; cat $O/dsp_pmc_traffic.txt
-# 2. bench line (with cpu baseline), plain
-python $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+# 2. bench line with all its extras (--full: rooflines, pop 512, cpu baseline)
+python $R/bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 # 3. kernel trace + stats of the same command (shorter)
-rocprofv3 --kernel-trace --stats -d $O/prof -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pop512 > $O/bench_prof.json 2> $O/prof.log
+rocprofv3 --kernel-trace --stats -d $O/prof -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-pop512 > $O/bench_prof.json 2> $O/prof.log
 python $R/profiles/summarize_rocprof.py $O/prof/*/*_results.db > $O/kernel_stats.txt
 # 4. EA-side counters of the conv launches (requests, in-flight level -> latency) + the Infinity-Cache / HBM calibration curve under the same counters
 STITO_GRAPH=0 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_32B_sum --kernel-trace -d $O/ea1 -- $BENCH_PMC > $O/ea1.log 2>&1
