@@ -385,7 +385,7 @@ int stito_spectral_centroid(const float *audio_dev, int n_items, int channels, i
  * logmel_dev (n_items * channels, T, n_mels); per item: clamp to (max over the item's channels, bands and
  * frames) - top_db (torchaudio amplitude_to_DB); per frame: DCT with dct_dev (n_mels, n_mfcc); over frames:
  * mean, unbiased std, max per coefficient -> out_dev (n_items, channels * 3 * n_mfcc) = per channel
- * [mean | std | max], rows L2-normalised.  n_mfcc <= 32, T * n_mfcc floats must fit 128 KB of LDS. */
+ * [mean | std | max], rows L2-normalised.  n_mfcc <= 32; any number of frames T >= 2. */
 int stito_mfcc_stats(const float *logmel_dev, int n_items, int channels, int64_t n_frames, int n_mels,
                      const float *dct_dev, int n_mfcc, float top_db, float *out_dev, void *stream);
 

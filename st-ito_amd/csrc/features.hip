@@ -210,18 +210,31 @@ __global__ __launch_bounds__(256) void k_rms_crest(const float *__restrict__ aud
 }
 
 // ---- MFCC statistics (utils.py:116-159 on torchaudio.transforms.MFCC, restated: parity unpinned) ----
-// one workgroup per (item, channel): clamp, DCT per frame into LDS, then mean / unbiased std / max over frames
-__global__ __launch_bounds__(256) void k_mfcc_stats(const float *__restrict__ lm, int channels, int64_t T, int M,
-                                                    const float *__restrict__ dct /*(M, K)*/, int K, float top_db,
-                                                    float *__restrict__ out) {
-    extern __shared__ float mf[];  // [T][K]
-    __shared__ float red[4];
+// one workgroup per (item, channel) streams its frames twice: thread (f, k) = (tid / 32, tid % 32) owns coefficient k of the
+// frames t = f, f + 8, ...; pass 1 forms each frame's DCT for the sum and the max, pass 2 forms it again (same order of
+// operations, same bits) for the squared deviations from the mean.  Nothing per frame is kept, so any number of frames
+// runs; the sums are float64 and their eight partials are combined in a fixed order, so the result is deterministic.
+constexpr int MFCC_NT = 256, MFCC_KMAX = 32, MFCC_FL = MFCC_NT / MFCC_KMAX;
+
+__device__ __forceinline__ float mfcc_dct(const float *__restrict__ row, const float *__restrict__ dct, int M, int K, int k, float floor_db) {
+    float acc = 0.0f;
+    for (int m = 0; m < M; ++m) acc = fmaf(fmaxf(row[m], floor_db), dct[m * K + k], acc);
+    return acc;
+}
+
+__global__ __launch_bounds__(MFCC_NT) void k_mfcc_stats(const float *__restrict__ lm, int channels, int64_t T, int M,
+                                                        const float *__restrict__ dct /*(M, K)*/, int K, float top_db,
+                                                        float *__restrict__ out) {
+    __shared__ float red[MFCC_NT / 64];
+    __shared__ double part[MFCC_FL][MFCC_KMAX];
+    __shared__ float partmx[MFCC_FL][MFCC_KMAX];
+    __shared__ double mean_s[MFCC_KMAX];
     const int stream = blockIdx.x, item = stream / channels, ch = stream % channels, tid = threadIdx.x;
     // top_db floor: max of the item's dB mel spectrogram over its channels, frames and bands
     float mxv = -INFINITY;
     {
         const float *pi = lm + (int64_t)item * channels * T * M;
-        for (int64_t i = tid; i < (int64_t)channels * T * M; i += 256) mxv = fmaxf(mxv, pi[i]);
+        for (int64_t i = tid; i < (int64_t)channels * T * M; i += MFCC_NT) mxv = fmaxf(mxv, pi[i]);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mxv = fmaxf(mxv, __shfl_xor(mxv, o));
         if ((tid & 63) == 0) red[tid >> 6] = mxv;
@@ -230,24 +243,43 @@ __global__ __launch_bounds__(256) void k_mfcc_stats(const float *__restrict__ lm
     }
     const float floor_db = mxv - top_db;
     const float *p = lm + (int64_t)stream * T * M;
-    for (int64_t q = tid; q < T * K; q += 256) {
-        const int64_t t = q / K;
-        const int k = (int)(q % K);
-        float acc = 0.0f;
-        for (int m = 0; m < M; ++m) acc = fmaf(fmaxf(p[t * M + m], floor_db), dct[m * K + k], acc);
-        mf[q] = acc;
-    }
+    const int k = tid % MFCC_KMAX, f = tid / MFCC_KMAX;
+    const bool act = k < K;
+    double s = 0.0;
+    float mx = -INFINITY;
+    if (act)
+        for (int64_t t = f; t < T; t += MFCC_FL) {
+            const float v = mfcc_dct(p + t * M, dct, M, K, k, floor_db);
+            s += (double)v;
+            mx = fmaxf(mx, v);
+        }
+    part[f][k] = s;
+    partmx[f][k] = mx;
     __syncthreads();
     if (tid < K) {
-        float s = 0.0f, mx = -INFINITY;
-        for (int64_t t = 0; t < T; ++t) { const float v = mf[t * K + tid]; s += v; mx = fmaxf(mx, v); }
-        const float mean = s / (float)T;
-        float ss = 0.0f;
-        for (int64_t t = 0; t < T; ++t) { const float d = mf[t * K + tid] - mean; ss = fmaf(d, d, ss); }
+        double st = 0.0;
+        float mt = -INFINITY;
+        for (int q = 0; q < MFCC_FL; ++q) { st += part[q][tid]; mt = fmaxf(mt, partmx[q][tid]); }
+        mean_s[tid] = st / (double)T;
+        partmx[0][tid] = mt;
+    }
+    __syncthreads();
+    const double mean = act ? mean_s[k] : 0.0;
+    double ss = 0.0;
+    if (act)
+        for (int64_t t = f; t < T; t += MFCC_FL) {
+            const double d = (double)mfcc_dct(p + t * M, dct, M, K, k, floor_db) - mean;
+            ss = fma(d, d, ss);
+        }
+    part[f][k] = ss;
+    __syncthreads();
+    if (tid < K) {
+        double sst = 0.0;
+        for (int q = 0; q < MFCC_FL; ++q) sst += part[q][tid];
         float *o = out + ((int64_t)item * channels + ch) * 3 * K;
-        o[tid] = mean;
-        o[K + tid] = sqrtf(ss / (float)(T - 1));
-        o[2 * K + tid] = mx;
+        o[tid] = (float)mean_s[tid];
+        o[K + tid] = (float)sqrt(sst / (double)(T - 1));
+        o[2 * K + tid] = partmx[0][tid];
     }
 }
 
@@ -259,11 +291,8 @@ extern "C" int stito_mfcc_stats(const float *logmel_dev, int n_items, int channe
                                 const float *dct_dev, int n_mfcc, float top_db, float *out_dev, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     STITO_REQUIRE(n_items > 0 && channels > 0 && n_frames > 1 && n_mels > 0, STITO_E_INVALID, "stito_mfcc_stats: empty input");
-    STITO_REQUIRE(n_mfcc > 0 && n_mfcc <= 32, STITO_E_UNSUPPORTED, "n_mfcc %d not in [1, 32]", n_mfcc);
-    const size_t lds = (size_t)n_frames * n_mfcc * sizeof(float);
-    STITO_REQUIRE(lds <= 128 * 1024, STITO_E_UNSUPPORTED, "MFCC statistics: %lld frames do not fit the LDS", (long long)n_frames);
-    STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mfcc_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_mfcc_stats, dim3(n_items * channels), dim3(256), lds, st, logmel_dev, channels, n_frames, n_mels, dct_dev,
+    STITO_REQUIRE(n_mfcc > 0 && n_mfcc <= MFCC_KMAX, STITO_E_UNSUPPORTED, "n_mfcc %d not in [1, 32]", n_mfcc);
+    hipLaunchKernelGGL(k_mfcc_stats, dim3(n_items * channels), dim3(MFCC_NT), 0, st, logmel_dev, channels, n_frames, n_mels, dct_dev,
                        n_mfcc, top_db, out_dev);
     STITO_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_l2norm_rows, dim3((n_items + 63) / 64), dim3(64), 0, st, out_dev, n_items, channels * 3 * n_mfcc);
