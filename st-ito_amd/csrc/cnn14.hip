@@ -1007,11 +1007,10 @@ static int wino_ttw(const ConvShape &c, bool pool) {
     return tc >= 8 ? 8 : (tc >= 4 ? 4 : 2);
 }
 
-static bool wino_supported(const ConvShape &c, bool pool) {
-    if (c.Cin % WK != 0 || c.Cout % 64 != 0) return false;
+// the geometry of the shape's tile-row width (false: the map does not fit the LDS-resident halo patch)
+static bool wino_geometry_any(const ConvShape &c, bool pool, int64_t &blocks) {
     WinoGeom g;
     size_t lds;
-    int64_t blocks;
     const int ttw = wino_ttw(c, pool);
     if (pool) return ttw == 8 ? wino_geometry<8, true>(c, g, lds, blocks) : ttw == 4 ? wino_geometry<4, true>(c, g, lds, blocks) : wino_geometry<2, true>(c, g, lds, blocks);
     return ttw == 8 ? wino_geometry<8, false>(c, g, lds, blocks) : ttw == 4 ? wino_geometry<4, false>(c, g, lds, blocks) : wino_geometry<2, false>(c, g, lds, blocks);
@@ -1045,39 +1044,121 @@ static int conv_first(const float *in, const float *w, const float *scale, const
     return STITO_OK;
 }
 
+// ---- the algorithms of this file and the id table (conv_layout.h: ConvAlgo) ----
+
+static bool direct_supported(const ConvShape &c, bool pool) {
+    if (c.Cin == 1) return !pool && c.Cout % 8 == 0;
+    return c.Cin % 8 == 0 && c.Cout % 64 == 0;  // channel-blocked activations: 8 channels per block
+}
+
+static int pack_direct(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st) {
+    const int64_t n = (int64_t)cout * cin * 9;
+    hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w_oihw, cout, cin, CK, packed);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
+// direct: launch_conv's tiling -- (BM x BN) = (128 x 128) when cout % 128 == 0, else (256 x 64); TW by map width
+static double direct_issued_flops(const ConvShape &c, bool pool) {
+    const int BM = c.Cout % 128 == 0 ? 128 : 256, BN = c.Cout % 128 == 0 ? 128 : 64;
+    const int TW = c.W >= 16 ? 16 : (c.W >= 8 ? 8 : 4), TH = BM / TW;
+    const int Heff = pool ? 2 * (c.H / 2) : c.H;
+    const int64_t n_row_tiles = ((int64_t)c.S * Heff + TH - 1) / TH, n_col_tiles = (c.W + TW - 1) / TW;
+    return 2.0 * (double)(n_row_tiles * n_col_tiles) * (c.Cout / BN) * BM * BN * 9.0 * c.Cin;
+}
+
+static int launch_direct(const ConvArgs &a) {
+    if (a.c.Cout % 128 == 0) {
+        return a.pool ? launch_conv_tw<2, 2, true>(a.in, a.w, a.scale, a.shift, a.out, a.c, a.st)
+                      : launch_conv_tw<2, 2, false>(a.in, a.w, a.scale, a.shift, a.out, a.c, a.st);
+    }
+    return a.pool ? launch_conv_tw<4, 1, true>(a.in, a.w, a.scale, a.shift, a.out, a.c, a.st)
+                  : launch_conv_tw<4, 1, false>(a.in, a.w, a.scale, a.shift, a.out, a.c, a.st);
+}
+
+static int pack_wino(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st) {
+    STITO_REQUIRE(cin % WK == 0 && cout % 64 == 0, STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
+    const int64_t n = (int64_t)cout * cin;
+    hipLaunchKernelGGL(k_pack_wino, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w_oihw, cout, cin, packed);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
+// The entries of the direct kernel, the F(2x2,3x3) float32 kernel and the retired ids, and the table of all of them
+const ConvAlgo &conv_algo(int id) {
+    static const ConvAlgo direct = {
+        .name = "conv (direct)", .supported = direct_supported, .packed_floats = [](int cout, int cin) { return (size_t)cout * cin * 9; },
+        .pack = pack_direct, .issued_flops = direct_issued_flops, .launch = launch_direct};
+    static const ConvAlgo wino = {
+        .name = "conv (winograd)", .winograd = true,
+        .supported = [](const ConvShape &c, bool pool) {
+            int64_t blocks;
+            return c.Cin % WK == 0 && c.Cout % 64 == 0 && wino_geometry_any(c, pool, blocks);
+        },
+        .packed_floats = [](int cout, int cin) { return (size_t)cout * cin * 16; }, .pack = pack_wino,
+        .issued_flops = [](const ConvShape &c, bool pool) {
+            int64_t blocks = 0;
+            return wino_geometry_any(c, pool, blocks) ? 2.0 * (double)blocks * 64.0 * 64.0 * 16.0 * c.Cin : 0.0;
+        },
+        .launch = [](const ConvArgs &a) {
+            return a.pool ? launch_wino_tw<true>(a.in, a.w, a.scale, a.shift, a.out, a.c, a.st)
+                          : launch_wino_tw<false>(a.in, a.w, a.scale, a.shift, a.out, a.c, a.st);
+        }};
+    // 6 and 7 (see stito_hip.h): unsupported, no packing, refused by stito_cnn14_pack_conv and the workspace entry point -- the
+    // workspace-less stito_conv3x3_bn_relu has never checked for them and runs them as the direct kernel
+    static const ConvAlgo retired = {
+        .name = "retired", .retired = true, .supported = [](const ConvShape &, bool) { return false; },
+        .packed_floats = [](int, int) { return (size_t)0; }, .launch = launch_direct};
+    switch (id) {
+        case STITO_CONV_DIRECT: return direct;
+        case STITO_CONV_WINOGRAD: return wino;
+        case STITO_CONV_WINOGRAD_F4: return wino43_algo();
+        case STITO_CONV_WINOGRAD_F4_PRE: return wino43_pre_algo();
+        case STITO_CONV_WINOGRAD_F4_SPLIT: return wino43_split_algo();
+        case STITO_CONV_WINOGRAD_F4_SPLIT2: return wino43_split2_algo();
+        case 6: case 7: return retired;
+        case STITO_CONV_WINOGRAD_F2_REG: return wino23r_algo();
+        case STITO_CONV_WINOGRAD_F4_SPLIT3: return wino43_split3_algo();
+        default: return direct;   // unknown ids: answered and launched as the direct kernel
+    }
+}
+
+// stito_conv3x3_bn_relu, and the workspace entry point for the algorithms that need no workspace
+static int conv3x3(const ConvAlgo &a, const ConvArgs &x) {
+    const ConvShape &c = x.c;
+    STITO_REQUIRE(c.S > 0 && c.H > 0 && c.W > 0, STITO_E_INVALID, "conv: empty input");
+    STITO_REQUIRE(!a.needs_workspace(), STITO_E_WORKSPACE,
+                  "conv: STITO_CONV_WINOGRAD_F4_PRE / _F4_SPLIT* / STITO_CONV_WINOGRAD_F2_REG need stito_conv3x3_bn_relu_ws");
+    if (c.Cin % 8 != 0) {
+        STITO_REQUIRE(c.Cin == 1 && !x.pool, STITO_E_UNSUPPORTED, "conv: cin=%d (only 1 or a multiple of 8)", c.Cin);
+        return conv_first(x.in, x.w, x.scale, x.shift, x.out, c.S, c.H, c.W, c.Cout, x.st, x.amax_out);
+    }
+    STITO_REQUIRE(c.Cout % 64 == 0, STITO_E_UNSUPPORTED, "conv: cout=%d must be a multiple of 64", c.Cout);
+    STITO_REQUIRE(!x.pool || (c.H >= 2 && c.W >= 2), STITO_E_INVALID, "Given input size: (%dx%dx%d). Output size is too small", c.Cout, c.H, c.W);
+    return a.launch(x);
+}
+
+// amax_in / amax_out: see ConvArgs (per-stream output maxima handed from one layer to the next inside the trunk)
+static int conv3x3_ws(int algo, const ConvArgs &x) {
+    const ConvAlgo &a = conv_algo(algo);
+    STITO_REQUIRE(!a.retired, STITO_E_UNSUPPORTED, "conv: algorithm %d was retired in ABI version 9", algo);
+    // (the first conv, cin == 1, runs a kernel of its own whatever the algorithm, and that one reports them)
+    STITO_REQUIRE(x.amax_out == nullptr || a.reports_amax || x.c.Cin == 1, STITO_E_INVALID, "conv: this algorithm does not report output maxima");
+    if (!a.needs_workspace()) return conv3x3(a, x);
+    STITO_REQUIRE(x.c.S > 0 && x.c.H > 0 && x.c.W > 0, STITO_E_INVALID, "conv: empty input");
+    return a.launch(x);
+}
+
 }  // namespace stito
 
 using namespace stito;
 
-static bool wino_ok(int cout, int cin) { return cin % WK == 0 && cout % 64 == 0; }
-
-extern "C" size_t stito_cnn14_packed_conv_floats(int cout, int cin, int algo) {
-    if (algo == 6 || algo == 7) return 0;  // retired (see stito_hip.h)
-    if (algo == STITO_CONV_WINOGRAD_F2_REG) return wino23r_packed_floats(cout, cin);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT || algo == STITO_CONV_WINOGRAD_F4_SPLIT2 || algo == STITO_CONV_WINOGRAD_F4_SPLIT3) return wino43_split_packed_floats(cout, cin);
-    return (size_t)cout * cin * ((algo == STITO_CONV_WINOGRAD_F4 || algo == STITO_CONV_WINOGRAD_F4_PRE) ? 36 : algo == STITO_CONV_WINOGRAD ? 16 : 9);
-}
+extern "C" size_t stito_cnn14_packed_conv_floats(int cout, int cin, int algo) { return conv_algo(algo).packed_floats(cout, cin); }
 
 extern "C" int stito_cnn14_pack_conv(const float *w_oihw_dev, int cout, int cin, int algo, float *packed_dev, void *stream) {
-    STITO_REQUIRE(algo != 6 && algo != 7, STITO_E_UNSUPPORTED, "conv: algorithm %d was retired in ABI version 9", algo);
-    if (algo == STITO_CONV_WINOGRAD_F2_REG) return pack_wino23r(w_oihw_dev, cout, cin, packed_dev, (hipStream_t)stream);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT || algo == STITO_CONV_WINOGRAD_F4_SPLIT2 || algo == STITO_CONV_WINOGRAD_F4_SPLIT3)
-        return pack_wino43_split(w_oihw_dev, cout, cin, packed_dev, algo == STITO_CONV_WINOGRAD_F4_SPLIT3 ? 2 : algo == STITO_CONV_WINOGRAD_F4_SPLIT2 ? 1 : 0,
-                                 (hipStream_t)stream);
-    if (algo == STITO_CONV_WINOGRAD_F4 || algo == STITO_CONV_WINOGRAD_F4_PRE) {  // one packing for both
-        STITO_REQUIRE(wino_ok(cout, cin), STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
-        return pack_wino43(w_oihw_dev, cout, cin, packed_dev, (hipStream_t)stream);
-    }
-    if (algo == STITO_CONV_WINOGRAD) {
-        STITO_REQUIRE(wino_ok(cout, cin), STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
-        const int64_t n = (int64_t)cout * cin;
-        hipLaunchKernelGGL(k_pack_wino, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_oihw_dev, cout, cin, packed_dev);
-    } else {
-        const int64_t n = (int64_t)cout * cin * 9;
-        hipLaunchKernelGGL(k_pack_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_oihw_dev, cout, cin, CK, packed_dev);
-    }
-    STITO_LAUNCH_CHECK();
-    return STITO_OK;
+    const ConvAlgo &a = conv_algo(algo);
+    STITO_REQUIRE(!a.retired, STITO_E_UNSUPPORTED, "conv: algorithm %d was retired in ABI version 9", algo);
+    return a.pack(w_oihw_dev, cout, cin, packed_dev, (hipStream_t)stream);
 }
 
 extern "C" size_t stito_cnn14_packed_conv1_f2reg_floats(void) { return conv1_f2reg_packed_floats(); }
@@ -1127,137 +1208,34 @@ extern "C" int stito_debug_wino_trace(long long *buf_dev) {
 extern "C" int stito_conv3x3_supported(int n, int H, int W, int cin, int cout, int pool, int algo) {
     if (n <= 0 || H <= 0 || W <= 0 || cout % 4 != 0) return 0;
     if (pool && (H < 2 || W < 2)) return 0;
-    if (algo == STITO_CONV_WINOGRAD_F4_PRE && (cout % 256 != 0 || (cout >= 1024 && cout % 512 != 0))) return 0;  // its workgroup order deals channel tiles in fours / eights
-    if (algo == 6 || algo == 7) return 0;  // retired
-    if (algo == STITO_CONV_WINOGRAD_F2_REG) return wino23r_supported(ConvShape{n, H, W, cin, cout}, pool != 0) ? 1 : 0;
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT3) return wino43_split3_supported(ConvShape{n, H, W, cin, cout}, pool != 0) ? 1 : 0;
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT || algo == STITO_CONV_WINOGRAD_F4_SPLIT2)
-        return (cout < 1024 || cout % 512 == 0) && wino43_split_supported(ConvShape{n, H, W, cin, cout}, pool != 0) ? 1 : 0;
-    if (algo == STITO_CONV_WINOGRAD_F4 || algo == STITO_CONV_WINOGRAD_F4_PRE) return wino43_supported(ConvShape{n, H, W, cin, cout}, pool != 0) ? 1 : 0;
-    if (algo == STITO_CONV_WINOGRAD) return wino_supported(ConvShape{n, H, W, cin, cout}, pool != 0) ? 1 : 0;
-    if (cin == 1) return (!pool && cout % 8 == 0) ? 1 : 0;
-    return (cin % 8 == 0 && cout % 64 == 0) ? 1 : 0;  // channel-blocked activations: 8 channels per block
+    return conv_algo(algo).supported(ConvShape{n, H, W, cin, cout}, pool != 0) ? 1 : 0;
 }
 
 // FLOPs of the MFMA instructions one launch issues, tile padding included (bench.py "roofline": the hardware-side
 // numerator, <= peak by construction; the algorithmic count 2*9*cin*cout*H*W is larger for the Winograd kernels)
 extern "C" double stito_conv3x3_issued_flops(int n, int H, int W, int cin, int cout, int pool, int algo) {
     if (!stito_conv3x3_supported(n, H, W, cin, cout, pool, algo) || cin % 8 != 0) return 0.0;
-    ConvShape c{n, H, W, cin, cout};
-    if (algo == STITO_CONV_WINOGRAD_F2_REG) return wino23r_issued_flops(c, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD_F4 || algo == STITO_CONV_WINOGRAD_F4_PRE) return wino43_issued_flops(c, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT) return 3.0 * wino43_issued_flops(c, pool != 0);  // hi hi' + hi lo' + lo hi' on the f16 pipe
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT2) return wino43_split2_issued_flops(c, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT3) return wino43_split3_issued_flops(c, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD) {
-        WinoGeom g;
-        size_t lds;
-        int64_t blocks = 0;
-        const int ttw = wino_ttw(c, pool != 0);
-        const bool ok = pool ? (ttw == 8 ? wino_geometry<8, true>(c, g, lds, blocks) : ttw == 4 ? wino_geometry<4, true>(c, g, lds, blocks) : wino_geometry<2, true>(c, g, lds, blocks))
-                             : (ttw == 8 ? wino_geometry<8, false>(c, g, lds, blocks) : ttw == 4 ? wino_geometry<4, false>(c, g, lds, blocks) : wino_geometry<2, false>(c, g, lds, blocks));
-        return ok ? 2.0 * (double)blocks * 64.0 * 64.0 * 16.0 * cin : 0.0;
-    }
-    // direct: launch_conv's tiling -- (BM x BN) = (128 x 128) when cout % 128 == 0, else (256 x 64); TW by map width
-    const int BM = cout % 128 == 0 ? 128 : 256, BN = cout % 128 == 0 ? 128 : 64;
-    const int TW = W >= 16 ? 16 : (W >= 8 ? 8 : 4), TH = BM / TW;
-    const int Heff = pool ? 2 * (H / 2) : H;
-    const int64_t n_row_tiles = ((int64_t)n * Heff + TH - 1) / TH, n_col_tiles = (W + TW - 1) / TW;
-    return 2.0 * (double)(n_row_tiles * n_col_tiles) * (cout / BN) * BM * BN * 9.0 * cin;
+    return conv_algo(algo).issued_flops(ConvShape{n, H, W, cin, cout}, pool != 0);
 }
 
 extern "C" int stito_conv3x3_bn_relu(const float *in_dev, const float *packed_w_dev, const float *scale_dev,
                                      const float *shift_dev, float *out_dev, int n, int H, int W, int cin, int cout,
                                      int pool, int algo, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    STITO_REQUIRE(n > 0 && H > 0 && W > 0, STITO_E_INVALID, "conv: empty input");
-    STITO_REQUIRE(algo != STITO_CONV_WINOGRAD_F4_PRE && algo != STITO_CONV_WINOGRAD_F4_SPLIT && algo != STITO_CONV_WINOGRAD_F4_SPLIT2 && algo != STITO_CONV_WINOGRAD_F4_SPLIT3 &&
-                  algo != STITO_CONV_WINOGRAD_F2_REG, STITO_E_WORKSPACE,
-                  "conv: STITO_CONV_WINOGRAD_F4_PRE / _F4_SPLIT* / STITO_CONV_WINOGRAD_F2_REG need stito_conv3x3_bn_relu_ws");
-    if (cin % 8 != 0) {
-        STITO_REQUIRE(cin == 1 && !pool, STITO_E_UNSUPPORTED, "conv: cin=%d (only 1 or a multiple of 8)", cin);
-        return conv_first(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, n, H, W, cout, st);
-    }
-    STITO_REQUIRE(cout % 64 == 0, STITO_E_UNSUPPORTED, "conv: cout=%d must be a multiple of 64", cout);
-    STITO_REQUIRE(!pool || (H >= 2 && W >= 2), STITO_E_INVALID, "Given input size: (%dx%dx%d). Output size is too small", cout, H, W);
-    ConvShape g{n, H, W, cin, cout};
-    if (algo == STITO_CONV_WINOGRAD_F4) {
-        STITO_REQUIRE(wino_ok(cout, cin), STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
-        return launch_wino43(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, pool != 0, g_wino_trace, st);
-    }
-    if (algo == STITO_CONV_WINOGRAD) {
-        STITO_REQUIRE(wino_ok(cout, cin), STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
-        return pool ? launch_wino_tw<true>(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, st)
-                    : launch_wino_tw<false>(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, st);
-    }
-    if (cout % 128 == 0) {
-        return pool ? launch_conv_tw<2, 2, true>(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, st)
-                    : launch_conv_tw<2, 2, false>(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, st);
-    }
-    return pool ? launch_conv_tw<4, 1, true>(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, st)
-                : launch_conv_tw<4, 1, false>(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, g, st);
+    return conv3x3(conv_algo(algo), ConvArgs{in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0, nullptr, 0,
+                                             (hipStream_t)stream, nullptr, nullptr, g_wino_trace});
 }
 
 extern "C" size_t stito_conv3x3_workspace_bytes(int n, int H, int W, int cin, int cout, int pool, int algo) {
-    if ((algo != STITO_CONV_WINOGRAD_F4_PRE && algo != STITO_CONV_WINOGRAD_F4_SPLIT && algo != STITO_CONV_WINOGRAD_F4_SPLIT2 && algo != STITO_CONV_WINOGRAD_F4_SPLIT3 &&
-         algo != STITO_CONV_WINOGRAD_F2_REG) || !stito_conv3x3_supported(n, H, W, cin, cout, pool, algo)) return 0;
-    if (algo == STITO_CONV_WINOGRAD_F2_REG) return wino23r_workspace_bytes(ConvShape{n, H, W, cin, cout}, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT) return wino43_split_workspace_bytes(ConvShape{n, H, W, cin, cout}, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT2) return wino43_split2_workspace_bytes(ConvShape{n, H, W, cin, cout}, pool != 0);
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT3) return wino43_split3_workspace_bytes(ConvShape{n, H, W, cin, cout}, pool != 0);
-    return wino43_pre_workspace_bytes(ConvShape{n, H, W, cin, cout}, pool != 0);
-}
-
-// amax_in / amax_out: see conv_layout.h (per-stream output maxima handed from one layer to the next inside the trunk)
-static int conv3x3_ws(const float *in_dev, const float *packed_w_dev, const float *scale_dev, const float *shift_dev, float *out_dev,
-                      int n, int H, int W, int cin, int cout, int pool, int algo, void *workspace_dev, size_t workspace_bytes,
-                      void *stream, const unsigned *amax_in, unsigned *amax_out) {
-    STITO_REQUIRE(algo != 6 && algo != 7, STITO_E_UNSUPPORTED, "conv: algorithm %d was retired in ABI version 9", algo);
-    if (algo == STITO_CONV_WINOGRAD_F2_REG) {
-        STITO_REQUIRE(n > 0 && H > 0 && W > 0, STITO_E_INVALID, "conv: empty input");
-        STITO_REQUIRE(stito_conv3x3_supported(n, H, W, cin, cout, pool, algo), STITO_E_UNSUPPORTED,
-                      "conv (winograd F(2x2,3x3), register-resident weights): %dx%d map, %d -> %d channels not covered (cin == 64, cout %% 64)", H, W, cin, cout);
-        STITO_REQUIRE(!pool || (H >= 2 && W >= 2), STITO_E_INVALID, "Given input size: (%dx%dx%d). Output size is too small", cout, H, W);
-        return launch_wino23r(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0, workspace_dev,
-                              workspace_bytes, (hipStream_t)stream, amax_in, amax_out);
-    }
-    if (algo == STITO_CONV_DIRECT && cin == 1 && amax_out != nullptr && !pool && n > 0 && H > 0 && W > 0)
-        return conv_first(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, n, H, W, cout, (hipStream_t)stream, amax_out);
-    if (algo != STITO_CONV_WINOGRAD_F4_PRE && algo != STITO_CONV_WINOGRAD_F4_SPLIT && algo != STITO_CONV_WINOGRAD_F4_SPLIT2 && algo != STITO_CONV_WINOGRAD_F4_SPLIT3) {
-        if (algo == STITO_CONV_WINOGRAD_F4 && amax_out != nullptr && n > 0 && H > 0 && W > 0 && cin % 8 == 0 && cout % 64 == 0 &&
-            wino_ok(cout, cin) && (!pool || (H >= 2 && W >= 2)))
-            return launch_wino43(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0, g_wino_trace,
-                                 (hipStream_t)stream, amax_out);
-        STITO_REQUIRE(amax_out == nullptr, STITO_E_INVALID, "conv: this algorithm does not report output maxima");
-        return stito_conv3x3_bn_relu(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, n, H, W, cin, cout, pool, algo, stream);
-    }
-    STITO_REQUIRE(n > 0 && H > 0 && W > 0, STITO_E_INVALID, "conv: empty input");
-    if (algo == STITO_CONV_WINOGRAD_F4_SPLIT || algo == STITO_CONV_WINOGRAD_F4_SPLIT2 || algo == STITO_CONV_WINOGRAD_F4_SPLIT3) {
-        STITO_REQUIRE(stito_conv3x3_supported(n, H, W, cin, cout, pool, algo), STITO_E_UNSUPPORTED,
-                      "conv (split-precision winograd F(4x4,3x3)): %dx%d map, %d -> %d channels not covered (cin %% 64, cout %% 256)", H, W, cin, cout);
-        STITO_REQUIRE(!pool || (H >= 2 && W >= 2), STITO_E_INVALID, "Given input size: (%dx%dx%d). Output size is too small", cout, H, W);
-        if (algo == STITO_CONV_WINOGRAD_F4_SPLIT3)
-            return launch_wino43_split3(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0,
-                                        workspace_dev, workspace_bytes, (hipStream_t)stream, amax_in, amax_out);
-        if (algo == STITO_CONV_WINOGRAD_F4_SPLIT2)
-            return launch_wino43_split2(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0,
-                                        workspace_dev, workspace_bytes, (hipStream_t)stream, amax_in, amax_out);
-        return launch_wino43_split(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0,
-                                   workspace_dev, workspace_bytes, (hipStream_t)stream, amax_in, amax_out);
-    }
-    STITO_REQUIRE(cin % 8 == 0 && cout % 64 == 0 && wino_ok(cout, cin), STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
-    STITO_REQUIRE(stito_conv3x3_supported(n, H, W, cin, cout, pool, algo), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(4x4,3x3), hoisted input transform): %dx%d map, %d -> %d channels not covered (cout must be a multiple of 256)", H, W, cin, cout);
-    STITO_REQUIRE(!pool || (H >= 2 && W >= 2), STITO_E_INVALID, "Given input size: (%dx%dx%d). Output size is too small", cout, H, W);
-    return launch_wino43_pre(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0,
-                             (float *)workspace_dev, workspace_bytes, (hipStream_t)stream, amax_out);
+    const ConvAlgo &a = conv_algo(algo);
+    if (!a.needs_workspace() || !stito_conv3x3_supported(n, H, W, cin, cout, pool, algo)) return 0;
+    return a.workspace_bytes(ConvShape{n, H, W, cin, cout}, pool != 0);
 }
 
 extern "C" int stito_conv3x3_bn_relu_ws(const float *in_dev, const float *packed_w_dev, const float *scale_dev,
                                         const float *shift_dev, float *out_dev, int n, int H, int W, int cin, int cout,
                                         int pool, int algo, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    return conv3x3_ws(in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, n, H, W, cin, cout, pool, algo, workspace_dev, workspace_bytes,
-                      stream, nullptr, nullptr);
+    return conv3x3_ws(algo, ConvArgs{in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0, workspace_dev,
+                                     workspace_bytes, (hipStream_t)stream, nullptr, nullptr, g_wino_trace});
 }
 
 static void cnn14_dims(int64_t T, int M, int H[7], int W[7]) {
@@ -1266,13 +1244,12 @@ static void cnn14_dims(int64_t T, int M, int H[7], int W[7]) {
     H[6] = H[5]; W[6] = W[5];
 }
 
-// transformed-input workspace: the largest need among the layers that run STITO_CONV_WINOGRAD_F4_PRE
+// the conv workspace: the largest need among the layers whose algorithm needs one (and conv_block1 in one launch)
 static size_t cnn14_pre_bytes(const stito_cnn14_weights *w, int n_streams, const int H[7], const int W[7]) {
     size_t v = 0;
     for (int i = 0; i < STITO_CNN14_NUM_CONVS; ++i) {
         const int algo = w->conv_wino_algo[i];
-        if (w->conv_wino_dev[i] == nullptr || (algo != STITO_CONV_WINOGRAD_F4_PRE && algo != STITO_CONV_WINOGRAD_F4_SPLIT && algo != STITO_CONV_WINOGRAD_F4_SPLIT2 && algo != STITO_CONV_WINOGRAD_F4_SPLIT3 &&
-                                               algo != STITO_CONV_WINOGRAD_F2_REG)) continue;
+        if (w->conv_wino_dev[i] == nullptr || !conv_algo(algo).needs_workspace()) continue;
         const int blk = i / 2, j = i % 2;
         const int ci = j == 0 ? w->channels[blk] : w->channels[blk + 1], pool = (j == 1 && blk < 5) ? 1 : 0;
         size_t need = stito_conv3x3_workspace_bytes(n_streams, H[blk], W[blk], ci, w->channels[blk + 1], pool, algo);
@@ -1453,9 +1430,7 @@ struct Trunk {
         const int nb = (i + 1) / 2, nj = (i + 1) % 2;
         const int nci = nj == 0 ? w->channels[nb] : w->channels[nb + 1], npool = (nj == 1 && nb < 5) ? 1 : 0;
         const int nalgo = w->conv_wino_algo[i + 1];
-        return w->conv_wino_dev[i + 1] != nullptr &&
-               (nalgo == STITO_CONV_WINOGRAD_F4_SPLIT || nalgo == STITO_CONV_WINOGRAD_F4_SPLIT2 || nalgo == STITO_CONV_WINOGRAD_F4_SPLIT3 ||
-                nalgo == STITO_CONV_WINOGRAD_F2_REG) &&
+        return w->conv_wino_dev[i + 1] != nullptr && conv_algo(nalgo).reads_amax &&
                stito_conv3x3_supported(S, H[nb], W[nb], nci, w->channels[nb + 1], npool, nalgo);
     }
 
@@ -1478,13 +1453,11 @@ struct Trunk {
         const int blk = i / 2, j = i % 2;
         const int cin = w->channels[blk], cout = w->channels[blk + 1];
         const int ci = j == 0 ? cin : cout, pool = (j == 1 && blk < 5) ? 1 : 0;
-        // Winograd where a transformed weight set was supplied and the map fits; direct otherwise
-        int walgo = (w->conv_wino_algo[i] == STITO_CONV_WINOGRAD_F4 || w->conv_wino_algo[i] == STITO_CONV_WINOGRAD_F4_PRE ||
-                     w->conv_wino_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT || w->conv_wino_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT2 || w->conv_wino_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT3 ||
-                     w->conv_wino_algo[i] == STITO_CONV_WINOGRAD_F2_REG)
-                        ? w->conv_wino_algo[i] : STITO_CONV_WINOGRAD;  // (a split packing has no float32 fallback: the direct kernel takes over)
-        if (walgo == STITO_CONV_WINOGRAD_F4_PRE && !stito_conv3x3_supported(S, H[blk], W[blk], ci, cout, pool, walgo))
-            walgo = STITO_CONV_WINOGRAD_F4;  // same packing
+        // Winograd where a transformed weight set was supplied and the map fits; direct otherwise.  An id that names no Winograd
+        // packing means the F(2x2,3x3) one.  (a split packing has no float32 fallback: the direct kernel takes over)
+        int walgo = conv_algo(w->conv_wino_algo[i]).winograd ? w->conv_wino_algo[i] : STITO_CONV_WINOGRAD;
+        const int same = conv_algo(walgo).same_packing;
+        if (same >= 0 && !stito_conv3x3_supported(S, H[blk], W[blk], ci, cout, pool, walgo)) walgo = same;
         const float *wino_w = w->conv_wino_dev[i];
         if (walgo == STITO_CONV_WINOGRAD_F4_SPLIT3 && w->conv_alt_dev[i] != nullptr && w->conv_alt_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT2 &&
             4 * wino43_split3_workgroups(ConvShape{S, H[blk], W[blk], ci, cout}, pool != 0) < 3 * n_cus &&
@@ -1496,11 +1469,12 @@ struct Trunk {
         TimedLaunch t((hipStream_t)stream, g_conv_timing.on && ci % 8 == 0);
         STITO_TRY(t.begin(i));
         const int algo_i = wino ? walgo : STITO_CONV_DIRECT;
-        // can this layer's kernel report the maxima the next one wants?
+        // can this layer's kernel report the maxima the next one wants?  (the first conv's own kernel can)
         unsigned *amax_out = nullptr;
-        if ((algo_i >= STITO_CONV_WINOGRAD_F4 || (algo_i == STITO_CONV_DIRECT && ci == 1 && !pool)) && next_wants_amax(i, S)) amax_out = amax_of(i, s0);
-        const int rc = conv3x3_ws(in, wino ? wino_w : w->conv_w_dev[i], w->bn_scale_dev[i], w->bn_shift_dev[i], out, S, H[blk], W[blk], ci, cout, pool,
-                                  algo_i, vbuf, vbytes, stream, (have_amax && i > 0) ? amax_of(i - 1, s0) : nullptr, amax_out);
+        if ((conv_algo(algo_i).reports_amax || (ci == 1 && !pool)) && next_wants_amax(i, S)) amax_out = amax_of(i, s0);
+        const int rc = conv3x3_ws(algo_i, ConvArgs{in, wino ? wino_w : w->conv_w_dev[i], w->bn_scale_dev[i], w->bn_shift_dev[i], out,
+                                                   ConvShape{S, H[blk], W[blk], ci, cout}, pool != 0, vbuf, vbytes, (hipStream_t)stream,
+                                                   (have_amax && i > 0) ? amax_of(i - 1, s0) : nullptr, amax_out, g_wino_trace});
         if (rc) return rc;
         have_amax = amax_out != nullptr;
         return t.end();

@@ -75,44 +75,52 @@ __device__ __forceinline__ int fdiv(int a, const FDiv f, int &rem) {
     return q;
 }
 
-// conv_wino43.hip
-bool wino43_supported(const ConvShape &c, bool pool);
-double wino43_issued_flops(const ConvShape &c, bool pool);
+// ---- the 3x3-conv algorithms (the STITO_CONV_* ids of stito_hip.h): what the C entry points and the trunk know about each ----
+
+// One launch: `w` is the algorithm's packing; `ws` its workspace (stito_conv3x3_workspace_bytes) or NULL.
 // amax_out (or NULL): per stream, the layer's largest output as a bit pattern (atomicMax into a buffer the caller zeroed);
-// amax_in (or NULL): the same of the layer that produced `in` -- without it the split-precision launchers scan `in` themselves
-int launch_wino43(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                  bool pool, long long *trace, hipStream_t st, unsigned *amax_out = nullptr);
-int pack_wino43(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st);
-size_t wino43_pre_workspace_bytes(const ConvShape &c, bool pool);  // hoisted input transform: bytes of V slabs (0: unsupported)
-int launch_wino43_pre(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                      bool pool, float *vbuf, size_t vbuf_bytes, hipStream_t st, unsigned *amax_out = nullptr);
-// split-precision streaming kernel (f16 hi + lo operands, f32 accumulate)
-bool wino43_split_supported(const ConvShape &c, bool pool);
-size_t wino43_split_workspace_bytes(const ConvShape &c, bool pool);
-size_t wino43_split_packed_floats(int cout, int cin);
-int pack_wino43_split(const float *w_oihw, int cout, int cin, float *packed, int layout, hipStream_t st);  // 0: k_conv_wino43s, 1: s2, 2: s3
-size_t wino43_split2_workspace_bytes(const ConvShape &c, bool pool);
-double wino43_split2_issued_flops(const ConvShape &c, bool pool);
-int launch_wino43_split2(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                         bool pool, void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr);
-bool wino43_split3_supported(const ConvShape &c, bool pool);   // six sweeps, 128 x 128 workgroup tiles (cout % 512 == 0)
-size_t wino43_split3_workspace_bytes(const ConvShape &c, bool pool);
-double wino43_split3_issued_flops(const ConvShape &c, bool pool);
+// amax_in (or NULL): the same of the layer that produced `in` -- without it the algorithms that read maxima scan `in` themselves
+struct ConvArgs {
+    const float *in, *w, *scale, *shift;
+    float *out;
+    ConvShape c;
+    bool pool;
+    void *ws;
+    size_t ws_bytes;
+    hipStream_t st;
+    const unsigned *amax_in;
+    unsigned *amax_out;
+    long long *trace;   // stito_debug_wino_trace buffer or NULL (the float32 Winograd kernels' timeline builds)
+};
+
+struct ConvAlgo {
+    const char *name;            // in error messages
+    bool retired;                // (ABI version 9) unsupported, no packing, refused by the workspace entry
+    bool winograd;               // a packing stito_cnn14_weights.conv_wino_dev can hold
+    bool reads_amax;             // scales its transformed input by per-stream maxima of its input (amax_in)
+    bool reports_amax;           // can report per-stream maxima of its output (amax_out)
+    int same_packing = -1;       // the id that runs the same packing where this one does not cover the shape (-1: none)
+    // shape and channel checks of this algorithm; the C entry points have checked n, H, W > 0, cout % 4 and the pooled size
+    bool (*supported)(const ConvShape &c, bool pool);
+    size_t (*packed_floats)(int cout, int cin);
+    int (*pack)(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st);
+    double (*issued_flops)(const ConvShape &c, bool pool);      // for a supported shape with cin % 8 == 0
+    size_t (*workspace_bytes)(const ConvShape &c, bool pool);   // for a supported shape; NULL: needs no workspace
+    // without a workspace: after the checks of stito_conv3x3_bn_relu; with one: checks the shape and the workspace itself
+    int (*launch)(const ConvArgs &a);
+    bool needs_workspace() const { return workspace_bytes != nullptr; }
+};
+
+const ConvAlgo &conv_algo(int id);   // cnn14.hip; unknown ids: the direct kernel
+// (functions, not objects: hipcc would also emit a constant-initialised global on the device, host function pointers and all)
+const ConvAlgo &wino43_algo(), &wino43_pre_algo(), &wino43_split_algo(), &wino43_split2_algo(), &wino43_split3_algo();   // conv_wino43.hip
+const ConvAlgo &wino23r_algo();                                                                                            // conv_wino23r.hip
+
+// conv_wino43.hip: workgroups of the six-sweep kernel that have work (the trunk's choice between it and the two-sweep kernel)
 int64_t wino43_split3_workgroups(const ConvShape &c, bool pool);
-int launch_wino43_split3(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                         bool pool, void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr);
-int launch_wino43_split(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                        bool pool, void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr);
-// conv_wino23r.hip: Winograd F(2x2,3x3) on the f16 matrix pipe, weights resident in registers (the 64-input-channel layers)
-bool wino23r_supported(const ConvShape &c, bool pool);
-double wino23r_issued_flops(const ConvShape &c, bool pool);
-size_t wino23r_workspace_bytes(const ConvShape &c, bool pool);  // per-stream maxima of the input when the caller has none
-size_t wino23r_packed_floats(int cout, int cin);
-int pack_wino23r(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st);
-int launch_wino23r(const float *in, const float *wpk, const float *scale, const float *shift, float *out, const ConvShape &c, bool pool,
-                   void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in = nullptr, unsigned *amax_out = nullptr);
-// conv_block1 in one launch on that kernel: the first conv (1 -> 64 channels, bn1, ReLU) is computed on the matrix pipe into
-// the patch ring in the slots where the unfused kernel issues its copies (c: the second conv's shape)
+// conv_block1 in one launch on the register-resident F(2x2,3x3) kernel (conv_wino23r.hip): the first conv (1 -> 64 channels, bn1,
+// ReLU) is computed on the matrix pipe into the patch ring in the slots where the unfused kernel issues its copies (c: the second
+// conv's shape)
 bool wino23r_fused1_supported(const ConvShape &c, bool pool);
 size_t wino23r_fused1_workspace_bytes(const ConvShape &c, bool pool);
 size_t conv1_f2reg_packed_floats();

@@ -615,7 +615,7 @@ __global__ void k_pack_wino23r_scale(unsigned *hdr) {
 
 static int w23_nb(int cin) { return cin == 64 ? 2 : 0; }
 
-size_t wino23r_packed_floats(int cout, int cin) { return (size_t)16 * cout * cin + 64; }
+static size_t wino23r_packed_floats(int cout, int cin) { return (size_t)16 * cout * cin + 64; }
 
 // dynamic LDS of k_conv_wino23r<4, 2, ., FUSE1>: patch ring + Z exchange + BN constants (+ first-conv weights and two log-mel buffers)
 static size_t w23_lds_bytes(bool fuse1) {
@@ -631,7 +631,7 @@ static bool w23_device_fits(bool fuse1) {
     return device_info(d) == STITO_OK && (size_t)d.lds_per_block >= w23_lds_bytes(fuse1);
 }
 
-bool wino23r_supported(const ConvShape &c, bool pool) {
+static bool wino23r_supported(const ConvShape &c, bool pool) {
     if (w23_nb(c.Cin) == 0 || c.Cout % (32 * w23_nb(c.Cin)) != 0) return false;
     if (!w23_device_fits(false)) return false;
     if (pool && (c.H < 2 || c.W < 2)) return false;
@@ -641,19 +641,19 @@ bool wino23r_supported(const ConvShape &c, bool pool) {
     return groups > 0 && groups < (1ll << 22);  // fdiv range
 }
 
-size_t wino23r_workspace_bytes(const ConvShape &c, bool pool) {
+static size_t wino23r_workspace_bytes(const ConvShape &c, bool pool) {
     return wino23r_supported(c, pool) ? align_up((size_t)c.S * sizeof(unsigned), 256) : 0;  // stream maxima when the caller has none
 }
 
 // f16-pipe FLOPs the kernel issues: groups x 32 tiles x 16 positions x cin x cout x 3 products
-double wino23r_issued_flops(const ConvShape &c, bool pool) {
+static double wino23r_issued_flops(const ConvShape &c, bool pool) {
     if (!wino23r_supported(c, pool)) return 0.0;
     const int tr = pool ? c.H / 2 : (c.H + 1) / 2, tc = pool ? c.W / 2 : (c.W + 1) / 2;
     const double groups = (double)c.S * ((tr + 1) / 2) * ((tc + 15) / 16);
     return 3.0 * 2.0 * groups * 32.0 * 16.0 * c.Cin * c.Cout;
 }
 
-int pack_wino23r(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st) {
+static int pack_wino23r(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st) {
     const int nb = w23_nb(cin);
     STITO_REQUIRE(nb > 0 && cout % (32 * nb) == 0, STITO_E_UNSUPPORTED, "conv (winograd F(2x2,3x3), register-resident weights): cin %d / cout %d", cin, cout);
     const int64_t n = (int64_t)cout * cin;
@@ -759,14 +759,22 @@ static int launch_w23(const float *in, const float *wpk, const float *scale, con
     return STITO_OK;
 }
 
-int launch_wino23r(const float *in, const float *wpk, const float *scale, const float *shift, float *out, const ConvShape &c, bool pool,
-                   void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
-    STITO_REQUIRE(wino23r_supported(c, pool), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(2x2,3x3), register-resident weights): %dx%d map, %d -> %d channels not covered", c.H, c.W, c.Cin, c.Cout);
-    STITO_REQUIRE(amax_in != nullptr || (ws != nullptr && ws_bytes >= wino23r_workspace_bytes(c, pool)), STITO_E_WORKSPACE,
-                  "conv (winograd F(2x2,3x3), register-resident weights): workspace have %zu need %zu", ws_bytes, wino23r_workspace_bytes(c, pool));
-    return pool ? launch_w23<true>(in, wpk, scale, shift, out, c, (char *)ws, st, amax_in, amax_out)
-                : launch_w23<false>(in, wpk, scale, shift, out, c, (char *)ws, st, amax_in, amax_out);
+static int launch_wino23r(const ConvArgs &a) {
+    const ConvShape &c = a.c;
+    STITO_REQUIRE(wino23r_supported(c, a.pool), STITO_E_UNSUPPORTED, "%s: %dx%d map, %d -> %d channels not covered (cin == 64, cout %% 64)",
+                  wino23r_algo().name, c.H, c.W, c.Cin, c.Cout);
+    STITO_REQUIRE(a.amax_in != nullptr || (a.ws != nullptr && a.ws_bytes >= wino23r_workspace_bytes(c, a.pool)), STITO_E_WORKSPACE,
+                  "%s: workspace have %zu need %zu", wino23r_algo().name, a.ws_bytes, wino23r_workspace_bytes(c, a.pool));
+    return a.pool ? launch_w23<true>(a.in, a.w, a.scale, a.shift, a.out, c, (char *)a.ws, a.st, a.amax_in, a.amax_out)
+                  : launch_w23<false>(a.in, a.w, a.scale, a.shift, a.out, c, (char *)a.ws, a.st, a.amax_in, a.amax_out);
+}
+
+const ConvAlgo &wino23r_algo() {
+    static const ConvAlgo e = {
+        .name = "conv (winograd F(2x2,3x3), register-resident weights)", .winograd = true, .reads_amax = true, .reports_amax = true,
+        .supported = wino23r_supported, .packed_floats = wino23r_packed_floats, .pack = pack_wino23r, .issued_flops = wino23r_issued_flops,
+        .workspace_bytes = wino23r_workspace_bytes, .launch = launch_wino23r};
+    return e;
 }
 
 // ---- conv_block1 in one launch (FUSE1) ------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace stito {
 
@@ -1493,9 +1494,9 @@ __global__ void k_pack_wino43s_scale(unsigned *hdr) {
     hdr[2] = __float_as_uint(__builtin_ldexpf(1.0f, 14 - e));
 }
 
-size_t wino43_split_packed_floats(int cout, int cin) { return (size_t)36 * cout * cin + 64; }
+static size_t w43s_packed_floats(int cout, int cin) { return (size_t)36 * cout * cin + 64; }
 
-int pack_wino43_split(const float *w_oihw, int cout, int cin, float *packed, int layout, hipStream_t st) {
+static int pack_wino43_split(const float *w_oihw, int cout, int cin, float *packed, int layout, hipStream_t st) {  // 0: k_conv_wino43s, 1: s2, 2: s3
     STITO_REQUIRE(cin % 64 == 0 && cout % (layout == 2 ? 128 : 64) == 0, STITO_E_UNSUPPORTED, "conv (split-precision winograd): cin %d / cout %d", cin, cout);
     const int64_t n = (int64_t)cout * cin;
     unsigned *hdr = (unsigned *)(packed + (size_t)36 * cout * cin);
@@ -1514,6 +1515,20 @@ int pack_wino43_split(const float *w_oihw, int cout, int cin, float *packed, int
 static int w43_ttw(const ConvShape &c, bool pool) {
     const int tc = pool ? (c.W / 2 + 1) / 2 : (c.W + 3) / 4;
     return tc >= 8 ? 8 : (tc >= 4 ? 4 : (tc >= 2 ? 2 : 1));
+}
+
+// f(TTW, POOL) with the shape's tile-row width and the pooling as std::integral_constant arguments: the one place that maps them
+// onto the instantiations of the kernels
+template <class F>
+static auto w43_dispatch(const ConvShape &c, bool pool, F &&f) {
+    using P = std::true_type;
+    using N = std::false_type;
+    switch (w43_ttw(c, pool)) {
+        case 8: return pool ? f(std::integral_constant<int, 8>{}, P{}) : f(std::integral_constant<int, 8>{}, N{});
+        case 4: return pool ? f(std::integral_constant<int, 4>{}, P{}) : f(std::integral_constant<int, 4>{}, N{});
+        case 2: return pool ? f(std::integral_constant<int, 2>{}, P{}) : f(std::integral_constant<int, 2>{}, N{});
+        default: return pool ? f(std::integral_constant<int, 1>{}, P{}) : f(std::integral_constant<int, 1>{}, N{});
+    }
 }
 
 template <int TTW>
@@ -1548,32 +1563,34 @@ static bool w43_geometry(const ConvShape &c, bool pool, Wino43Geom &g, size_t &l
     return lds <= 160 * 1024 && (size_t)12 * 32 * W43_XT <= (size_t)2 * W43_BUF;
 }
 
-bool wino43_supported(const ConvShape &c, bool pool) {
+// the geometry of the shape's instantiation (false: the map does not fit the kernel's staging)
+static bool w43_geometry_any(const ConvShape &c, bool pool, Wino43Geom &g, size_t &lds, int64_t &blocks) {
+    return w43_dispatch(c, pool, [&](auto ttw, auto) { return w43_geometry<decltype(ttw)::value>(c, pool, g, lds, blocks); });
+}
+
+// the same for a launcher, as a status
+template <int TTW>
+static int w43_staging(const ConvShape &c, bool pool, Wino43Geom &g, size_t &lds, int64_t &blocks) {
+    STITO_REQUIRE((w43_geometry<TTW>(c, pool, g, lds, blocks)), STITO_E_UNSUPPORTED,
+                  "conv (winograd F(4x4,3x3)): %dx%d map, %d channels does not fit the kernel's staging", c.H, c.W, c.Cin);
+    return STITO_OK;
+}
+
+static bool wino43_supported(const ConvShape &c, bool pool) {
     if (c.Cin % 8 != 0 || c.Cout % 64 != 0) return false;
     if (pool && (c.H < 2 || c.W < 2)) return false;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    switch (w43_ttw(c, pool)) {
-        case 8: return w43_geometry<8>(c, pool, g, lds, blocks);
-        case 4: return w43_geometry<4>(c, pool, g, lds, blocks);
-        case 2: return w43_geometry<2>(c, pool, g, lds, blocks);
-        default: return w43_geometry<1>(c, pool, g, lds, blocks);
-    }
+    return w43_geometry_any(c, pool, g, lds, blocks);
 }
 
 // MFMA work the kernel issues for this shape (tile padding included): workgroups x 32 tiles x 64 channels x 36 positions x cin MACs
-double wino43_issued_flops(const ConvShape &c, bool pool) {
+static double wino43_issued_flops(const ConvShape &c, bool pool) {
     Wino43Geom g;
     size_t lds;
     int64_t blocks = 0;
-    bool ok;
-    switch (w43_ttw(c, pool)) {
-        case 8: ok = w43_geometry<8>(c, pool, g, lds, blocks); break;
-        case 4: ok = w43_geometry<4>(c, pool, g, lds, blocks); break;
-        case 2: ok = w43_geometry<2>(c, pool, g, lds, blocks); break;
-        default: ok = w43_geometry<1>(c, pool, g, lds, blocks); break;
-    }
+    const bool ok = w43_geometry_any(c, pool, g, lds, blocks);
     return ok ? 2.0 * (double)blocks * 32.0 * 64.0 * 36.0 * c.Cin : 0.0;
 }
 
@@ -1672,190 +1689,166 @@ static int w43_multi_queue_launch(int64_t blocks, hipStream_t st, LAUNCH &&launc
 }
 
 template <int TTW, bool POOL>
-static int launch_w43(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                      long long *trace, hipStream_t st, unsigned *amax_out) {
+static int launch_w43(const ConvArgs &a) {
+    const ConvShape &c = a.c;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    STITO_REQUIRE((w43_geometry<TTW>(c, POOL, g, lds, blocks)), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(4x4,3x3)): %dx%d map, %d channels does not fit the kernel's staging", c.H, c.W, c.Cin);
-    g.trace = trace;
-    g.amax_out = amax_out;
+    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
+    g.trace = a.trace;
+    g.amax_out = a.amax_out;
     W43_CLK_ARM(g)
-    auto kern = trace ? k_conv_wino43<TTW, POOL, true> : k_conv_wino43<TTW, POOL, false>;
+    auto kern = a.trace ? k_conv_wino43<TTW, POOL, true> : k_conv_wino43<TTW, POOL, false>;
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (trace != nullptr || (256 % (c.Cout / 64)) != 0) {   // (the timeline build stamps by blockIdx; grids are cut at multiples of 256 items = whole pixel blocks)
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W43_THREADS), lds, st, in, upk, scale, shift, out, g);
+    if (a.trace != nullptr || (256 % (c.Cout / 64)) != 0) {   // (the timeline build stamps by blockIdx; grids are cut at multiples of 256 items = whole pixel blocks)
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W43_THREADS), lds, a.st, a.in, a.w, a.scale, a.shift, a.out, g);
     } else {
-        STITO_TRY(w43_multi_queue_launch(blocks, st, [&](int64_t n_blk, int b0, hipStream_t q) {
+        STITO_TRY(w43_multi_queue_launch(blocks, a.st, [&](int64_t n_blk, int b0, hipStream_t q) {
             Wino43Geom gq = g;
             gq.b0 = b0;
-            hipLaunchKernelGGL(kern, dim3((unsigned)n_blk), dim3(W43_THREADS), lds, q, in, upk, scale, shift, out, gq);
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_blk), dim3(W43_THREADS), lds, q, a.in, a.w, a.scale, a.shift, a.out, gq);
         }, true));
     }
     STITO_LAUNCH_CHECK();
-    W43_CLK_REPORT("k_conv_wino43 (f32 MFMA)", c, st)
+    W43_CLK_REPORT("k_conv_wino43 (f32 MFMA)", c, a.st)
     return STITO_OK;
 }
 
-int launch_wino43(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                  bool pool, long long *trace, hipStream_t st, unsigned *amax_out) {
-    switch (w43_ttw(c, pool)) {
-        case 8: return pool ? launch_w43<8, true>(in, upk, scale, shift, out, c, trace, st, amax_out) : launch_w43<8, false>(in, upk, scale, shift, out, c, trace, st, amax_out);
-        case 4: return pool ? launch_w43<4, true>(in, upk, scale, shift, out, c, trace, st, amax_out) : launch_w43<4, false>(in, upk, scale, shift, out, c, trace, st, amax_out);
-        case 2: return pool ? launch_w43<2, true>(in, upk, scale, shift, out, c, trace, st, amax_out) : launch_w43<2, false>(in, upk, scale, shift, out, c, trace, st, amax_out);
-        default: return pool ? launch_w43<1, true>(in, upk, scale, shift, out, c, trace, st, amax_out) : launch_w43<1, false>(in, upk, scale, shift, out, c, trace, st, amax_out);
-    }
+// The input-transform pass of the hoisted and split-precision paths over m_blocks pixel blocks (blocks past the map transform to
+// zeros): MODE 2 writes f32 V slabs, MODE 3 / 4 / 5 the scaled f16 halves in the slab order of k_conv_wino43s / s2 / s3 (scaled by
+// the stream maxima `amax`).  The chunks of a pixel block split over as many workgroups as it takes to fill the chip a few times.
+template <int TTW, bool POOL, int MODE>
+static int w43_transform(const Wino43Geom &g, int64_t m_blocks, const float *in, const unsigned *amax, void *vbuf, hipStream_t st) {
+    Wino43Geom gv = g;
+    const int n_chunks = g.Cin / W43_K;
+    int ncg = 1;
+    while (m_blocks * ncg < 1024 && n_chunks % (4 * ncg) == 0 && n_chunks / (2 * ncg) >= 4) ncg *= 2;  // even share, >= 4 chunks
+    gv.n_cgroups = ncg;
+    auto kern = k_conv_wino43<TTW, POOL, false, MODE>;
+    const size_t lds_t = ((size_t)2 * W43_V + 2 * W43Patch<TTW>::PFL) * sizeof(float);  // V buffers + patch buffers (no weights)
+    STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(m_blocks * ncg)), dim3(W43_THREADS), lds_t, st, in, (const float *)nullptr,
+                       (const float *)amax, (const float *)nullptr, (float *)vbuf, gv);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
 }
 
-// Hoisted input transform (MODE 2 then MODE 1): V slabs [pixel block][cin/4][36][pair][32][2] in `vbuf`.
-template <int TTW>
-static size_t w43_pre_bytes(const ConvShape &c, bool pool) {
+// The stream maxima the split-precision transform scales by: amax_in when the layer that produced `in` reported them, else
+// scanned from `in` into amax_ws (zeroed first)
+static int w43_stream_amax(const ConvArgs &a, unsigned *amax_ws, const unsigned *&amax) {
+    amax = a.amax_in;
+    if (a.amax_in != nullptr) return STITO_OK;
+    const ConvShape &c = a.c;
+    amax = amax_ws;
+    STITO_TRY(zero_async(amax_ws, (size_t)c.S * sizeof(unsigned), a.st));
+    const int64_t per_stream = (int64_t)c.Cin * c.H * c.W;
+    int splits = (int)((per_stream / 4 + 256 * 16 - 1) / (256 * 16));  // >= 16 float4 per thread
+    const int cap = (4096 + c.S - 1) / c.S;                            // ~16 workgroups per CU in total
+    splits = splits > cap ? cap : (splits < 1 ? 1 : splits);
+    hipLaunchKernelGGL(k_stream_absmax, dim3((unsigned)splits, (unsigned)c.S), dim3(256), 0, a.st, a.in, per_stream, amax_ws);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
+// The launch of a workspace algorithm of this file: the shapes it covers, the workspace it needs, then launch(TTW, POOL)
+template <class L>
+static int w43_ws_launch(const ConvAlgo &algo, const char *family, const char *covers, const ConvArgs &a, L &&launch) {
+    const ConvShape &c = a.c;
+    STITO_REQUIRE(algo.supported(c, a.pool), STITO_E_UNSUPPORTED, "%s: %dx%d map, %d -> %d channels not covered (%s)", family, c.H, c.W, c.Cin,
+                  c.Cout, covers);
+    const size_t need = algo.workspace_bytes(c, a.pool);
+    STITO_REQUIRE(need > 0 && a.ws != nullptr && a.ws_bytes >= need, STITO_E_WORKSPACE, "%s: workspace have %zu need %zu", algo.name, a.ws_bytes, need);
+    return w43_dispatch(c, a.pool, launch);
+}
+
+// Hoisted input transform (MODE 2 then MODE 1): V slabs [pixel block][cin/4][36][pair][32][2] in the workspace.
+static size_t wino43_pre_workspace_bytes(const ConvShape &c, bool pool) {
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    if (!w43_geometry<TTW>(c, pool, g, lds, blocks)) return 0;
+    if (!wino43_supported(c, pool) || !w43_geometry_any(c, pool, g, lds, blocks)) return 0;
     return (size_t)(blocks / (c.Cout / 64)) * (size_t)(c.Cin / W43_K) * W43_V * sizeof(float);
 }
 
-size_t wino43_pre_workspace_bytes(const ConvShape &c, bool pool) {
-    if (!wino43_supported(c, pool)) return 0;
-    switch (w43_ttw(c, pool)) {
-        case 8: return w43_pre_bytes<8>(c, pool);
-        case 4: return w43_pre_bytes<4>(c, pool);
-        case 2: return w43_pre_bytes<2>(c, pool);
-        default: return w43_pre_bytes<1>(c, pool);
-    }
-}
-
 template <int TTW, bool POOL>
-static int launch_w43_pre(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                          float *vbuf, hipStream_t st, unsigned *amax_out) {
+static int launch_w43_pre(const ConvArgs &a) {
+    const ConvShape &c = a.c;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    STITO_REQUIRE((w43_geometry<TTW>(c, POOL, g, lds, blocks)), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(4x4,3x3)): %dx%d map, %d channels does not fit the kernel's staging", c.H, c.W, c.Cin);
-    {   // V slabs: the chunks of a pixel block split over as many workgroups as it takes to fill the chip a few times
-        Wino43Geom gv = g;
-        const int64_t m_blocks = blocks / (c.Cout / 64);
-        const int n_chunks = c.Cin / W43_K;
-        int ncg = 1;
-        while (m_blocks * ncg < 1024 && n_chunks % (4 * ncg) == 0 && n_chunks / (2 * ncg) >= 4) ncg *= 2;  // even share, >= 4 chunks
-        gv.n_cgroups = ncg;
-        auto kern = k_conv_wino43<TTW, POOL, false, 2>;
-        const size_t lds_t = ((size_t)2 * W43_V + 2 * W43Patch<TTW>::PFL) * sizeof(float);  // V buffers + patch buffers (no weights)
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(m_blocks * ncg)), dim3(W43_THREADS), lds_t, st, in, (const float *)nullptr,
-                           (const float *)nullptr, (const float *)nullptr, vbuf, gv);
-        STITO_LAUNCH_CHECK();
-    }
+    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
+    const int64_t m_blocks = blocks / (c.Cout / 64);
+    STITO_TRY((w43_transform<TTW, POOL, 2>(g, m_blocks, a.in, nullptr, a.ws, a.st)));
     auto kern = k_conv_wino43<TTW, POOL, false, 1>;
     const size_t lds1 = (size_t)2 * W43_BUF * sizeof(float);
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
     // grid in whole XCD rounds: 8 XCDs x (groups of 8 pixel blocks) x (groups of 4 channel tiles) x 32 workgroups
-    const int64_t m_blocks = blocks / (c.Cout / 64);
     g.n_mblocks = (int)m_blocks;
     // channel tiles side by side on an XCD: swept 1..32 at 512 streams (tools/conv_bench.py --modes 9): 4 is best for 8 tiles
     // (conv_block4: 3.17 / 5.69 ms against 3.63 / 6.59 for 1), 8 from 16 tiles up (1-4 % over 4), 32 loses 15 % at 32 tiles
     const int n_tiles = c.Cout / 64;
-    const int a = n_tiles >= 16 ? 8 : 4;
-    STITO_REQUIRE(n_tiles % a == 0, STITO_E_UNSUPPORTED, "conv (hoisted input transform): cout %d", c.Cout);
-    g.ct_group = a;
-    g.amax_out = amax_out;
-    const int bm = 32 / a;
+    const int ag = n_tiles >= 16 ? 8 : 4;
+    STITO_REQUIRE(n_tiles % ag == 0, STITO_E_UNSUPPORTED, "conv (hoisted input transform): cout %d", c.Cout);
+    g.ct_group = ag;
+    g.amax_out = a.amax_out;
+    const int bm = 32 / ag;
     const int64_t m_groups = ((m_blocks + 7) / 8 + bm - 1) / bm;
-    blocks = 8 * m_groups * (n_tiles / a) * 32;
+    blocks = 8 * m_groups * (n_tiles / ag) * 32;
     STITO_REQUIRE(blocks < (1ll << 31), STITO_E_UNSUPPORTED, "conv (hoisted input transform): grid");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W43_THREADS), lds1, st, (const float *)vbuf, upk, scale, shift, out, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W43_THREADS), lds1, a.st, (const float *)a.ws, a.w, a.scale, a.shift, a.out, g);
     STITO_LAUNCH_CHECK();
     return STITO_OK;
 }
 
-int launch_wino43_pre(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                      bool pool, float *vbuf, size_t vbuf_bytes, hipStream_t st, unsigned *amax_out) {
-    const size_t need = wino43_pre_workspace_bytes(c, pool);
-    STITO_REQUIRE(need > 0 && vbuf != nullptr && vbuf_bytes >= need, STITO_E_WORKSPACE,
-                  "conv (winograd F(4x4,3x3), hoisted input transform): workspace have %zu need %zu", vbuf_bytes, need);
-    switch (w43_ttw(c, pool)) {
-        case 8: return pool ? launch_w43_pre<8, true>(in, upk, scale, shift, out, c, vbuf, st, amax_out) : launch_w43_pre<8, false>(in, upk, scale, shift, out, c, vbuf, st, amax_out);
-        case 4: return pool ? launch_w43_pre<4, true>(in, upk, scale, shift, out, c, vbuf, st, amax_out) : launch_w43_pre<4, false>(in, upk, scale, shift, out, c, vbuf, st, amax_out);
-        case 2: return pool ? launch_w43_pre<2, true>(in, upk, scale, shift, out, c, vbuf, st, amax_out) : launch_w43_pre<2, false>(in, upk, scale, shift, out, c, vbuf, st, amax_out);
-        default: return pool ? launch_w43_pre<1, true>(in, upk, scale, shift, out, c, vbuf, st, amax_out) : launch_w43_pre<1, false>(in, upk, scale, shift, out, c, vbuf, st, amax_out);
-    }
-}
-
 // Split-precision variant of the hoisted path: stream maxima -> MODE 3 (V slabs as scaled f16 halves) -> k_conv_wino43s.
 // Workspace: the V slabs (the same bytes as MODE 2's) followed by one unsigned per stream.
-bool wino43_split_supported(const ConvShape &c, bool pool) {
+static bool wino43_split_supported(const ConvShape &c, bool pool) {
     return c.Cin % 64 == 0 && c.Cout % 256 == 0 && wino43_supported(c, pool) && ((int64_t)c.Cin * c.H * c.W) % 8 == 0;
 }
 
-size_t wino43_split_workspace_bytes(const ConvShape &c, bool pool) {
+static size_t wino43_split_workspace_bytes(const ConvShape &c, bool pool) {
     if (!wino43_split_supported(c, pool)) return 0;
     return align_up(wino43_pre_workspace_bytes(c, pool), 256) + align_up((size_t)c.S * sizeof(unsigned), 256);
 }
 
 template <int TTW, bool POOL>
-static int launch_w43_split(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                            char *ws, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
+static int launch_w43_split(const ConvArgs &a) {
+    const ConvShape &c = a.c;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    STITO_REQUIRE((w43_geometry<TTW>(c, POOL, g, lds, blocks)), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(4x4,3x3)): %dx%d map, %d channels does not fit the kernel's staging", c.H, c.W, c.Cin);
+    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
     const int64_t m_blocks = blocks / (c.Cout / 64);
-    const unsigned *amax = amax_in;
-    if (amax_in == nullptr) {   // stream maxima (not supplied by the layer that produced `in`)
-        unsigned *amax_ws = (unsigned *)(ws + align_up((size_t)m_blocks * (c.Cin / W43_K) * W43_V * sizeof(float), 256));
-        amax = amax_ws;
-        STITO_TRY(zero_async(amax_ws, (size_t)c.S * sizeof(unsigned), st));
-        const int64_t per_stream = (int64_t)c.Cin * c.H * c.W;
-        int splits = (int)((per_stream / 4 + 256 * 16 - 1) / (256 * 16));  // >= 16 float4 per thread
-        const int cap = (4096 + c.S - 1) / c.S;                            // ~16 workgroups per CU in total
-        splits = splits > cap ? cap : (splits < 1 ? 1 : splits);
-        hipLaunchKernelGGL(k_stream_absmax, dim3((unsigned)splits, (unsigned)c.S), dim3(256), 0, st, in, per_stream, amax_ws);
-        STITO_LAUNCH_CHECK();
-    }
-    {   // V slabs (MODE 3): grid as MODE 2
-        Wino43Geom gv = g;
-        const int n_chunks = c.Cin / W43_K;
-        int ncg = 1;
-        while (m_blocks * ncg < 1024 && n_chunks % (4 * ncg) == 0 && n_chunks / (2 * ncg) >= 4) ncg *= 2;
-        gv.n_cgroups = ncg;
-        auto kern = k_conv_wino43<TTW, POOL, false, 3>;
-        const size_t lds_t = ((size_t)2 * W43_V + 2 * W43Patch<TTW>::PFL) * sizeof(float);  // V buffers + patch buffers (no weights)
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(m_blocks * ncg)), dim3(W43_THREADS), lds_t, st, in, (const float *)nullptr,
-                           (const float *)amax, (const float *)nullptr, (float *)ws, gv);
-        STITO_LAUNCH_CHECK();
-    }
+    char *ws = (char *)a.ws;
+    const unsigned *amax;
+    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + align_up((size_t)m_blocks * (c.Cin / W43_K) * W43_V * sizeof(float), 256)), amax));
+    STITO_TRY((w43_transform<TTW, POOL, 3>(g, m_blocks, a.in, amax, ws, a.st)));
     auto kern = k_conv_wino43s<TTW, POOL>;
     const size_t lds1 = (size_t)3 * S43_SLAB;
     static_assert((size_t)12 * 32 * W43_XT * sizeof(float) <= (size_t)3 * S43_SLAB, "epilogue exchange fits the slab ring");
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
     g.n_mblocks = (int)m_blocks;
     const int n_tiles = c.Cout / 64;
-    int a = n_tiles >= 16 ? 8 : (n_tiles >= 8 ? 4 : 2);  // swept again with the round's final kernels (profiles/round3_stream_loop_experiments.txt, 15.)
-    if (const char *e = getenv("STITO_W43S_CTG")) { const int ae = atoi(e); if (ae >= 1 && ae <= 32 && (ae & (ae - 1)) == 0 && n_tiles % ae == 0) a = ae; }  // tuning aid (tools/conv_bench.py)
-    STITO_REQUIRE(a >= 1 && a <= 32 && (a & (a - 1)) == 0 && n_tiles % a == 0, STITO_E_UNSUPPORTED, "conv (split-precision winograd): cout %d", c.Cout);
-    g.ct_group = a;
-    const int bm = 32 / a;
+    int ag = n_tiles >= 16 ? 8 : (n_tiles >= 8 ? 4 : 2);  // swept again with the round's final kernels (profiles/round3_stream_loop_experiments.txt, 15.)
+    if (const char *e = getenv("STITO_W43S_CTG")) { const int ae = atoi(e); if (ae >= 1 && ae <= 32 && (ae & (ae - 1)) == 0 && n_tiles % ae == 0) ag = ae; }  // tuning aid (tools/conv_bench.py)
+    STITO_REQUIRE(ag >= 1 && ag <= 32 && (ag & (ag - 1)) == 0 && n_tiles % ag == 0, STITO_E_UNSUPPORTED, "conv (split-precision winograd): cout %d", c.Cout);
+    g.ct_group = ag;
+    const int bm = 32 / ag;
     const int64_t m_groups = ((m_blocks + 7) / 8 + bm - 1) / bm;
-    blocks = 8 * m_groups * (n_tiles / a) * 32;
+    blocks = 8 * m_groups * (n_tiles / ag) * 32;
     STITO_REQUIRE(blocks < (1ll << 31), STITO_E_UNSUPPORTED, "conv (split-precision winograd): grid");
-    g.amax_out = amax_out;
-    const float *u_inv = upk + (size_t)36 * c.Cout * c.Cin + 1;
+    g.amax_out = a.amax_out;
+    const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
     W43_CLK_ARM(g)
     // the layer as several grids on several hardware queues (w43_multi_queue_launch): the queues' dispatchers overlap the hand-over
-    STITO_TRY(w43_multi_queue_launch(blocks, st, [&](int64_t n_blk, int b0, hipStream_t q) {
+    STITO_TRY(w43_multi_queue_launch(blocks, a.st, [&](int64_t n_blk, int b0, hipStream_t q) {
         Wino43Geom gq = g;
         gq.b0 = b0;
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_blk), dim3(W43_THREADS), lds1, q, (const char *)ws, (const char *)upk, scale, shift, out, gq,
-                           (const unsigned *)amax, u_inv);
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_blk), dim3(W43_THREADS), lds1, q, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, gq,
+                           amax, u_inv);
     }));
     STITO_LAUNCH_CHECK();
-    W43_CLK_REPORT("k_conv_wino43s (f16 MFMA)", c, st)
+    W43_CLK_REPORT("k_conv_wino43s (f16 MFMA)", c, a.st)
     return STITO_OK;
 }
 
@@ -1889,12 +1882,7 @@ static int64_t w43_split2_grid(const ConvShape &c, bool pool, int64_t &m_pairs, 
 
 static int64_t w43_split2_grid_any(const ConvShape &c, bool pool, int64_t &m_pairs, int &ct_group) {
     int xm;
-    switch (w43_ttw(c, pool)) {
-        case 8: return w43_split2_grid<8>(c, pool, m_pairs, ct_group, xm);
-        case 4: return w43_split2_grid<4>(c, pool, m_pairs, ct_group, xm);
-        case 2: return w43_split2_grid<2>(c, pool, m_pairs, ct_group, xm);
-        default: return w43_split2_grid<1>(c, pool, m_pairs, ct_group, xm);
-    }
+    return w43_dispatch(c, pool, [&](auto ttw, auto) { return w43_split2_grid<decltype(ttw)::value>(c, pool, m_pairs, ct_group, xm); });
 }
 
 // the two sweeps of an item as two workgroups when that still fits one round of the device (see the kernel); STITO_W43S2_SWSPLIT=0 / 1 forces
@@ -1909,7 +1897,7 @@ static bool w43_split2_sweep_split(int64_t m_pairs, int cout, int cin) {
 }
 
 // f16-pipe FLOPs the two-sweep kernel issues: pixel-block pairs (a padded half included) x channel tiles x 64 x 64 x 36 x cin x 3 products
-double wino43_split2_issued_flops(const ConvShape &c, bool pool) {
+static double wino43_split2_issued_flops(const ConvShape &c, bool pool) {
     if (!wino43_split_supported(c, pool)) return 0.0;
     int64_t m_pairs = 0;
     int a;
@@ -1917,7 +1905,7 @@ double wino43_split2_issued_flops(const ConvShape &c, bool pool) {
     return 3.0 * 2.0 * (double)m_pairs * (c.Cout / 64) * 64.0 * 64.0 * 36.0 * c.Cin;
 }
 
-size_t wino43_split2_workspace_bytes(const ConvShape &c, bool pool) {
+static size_t wino43_split2_workspace_bytes(const ConvShape &c, bool pool) {
     if (!wino43_split_supported(c, pool)) return 0;
     int64_t m_pairs = 0;
     int a;
@@ -1928,88 +1916,52 @@ size_t wino43_split2_workspace_bytes(const ConvShape &c, bool pool) {
 }
 
 template <int TTW, bool POOL>
-static int launch_w43_split2(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                             char *ws, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
+static int launch_w43_split2(const ConvArgs &a) {
+    const ConvShape &c = a.c;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    STITO_REQUIRE((w43_geometry<TTW>(c, POOL, g, lds, blocks)), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(4x4,3x3)): %dx%d map, %d channels does not fit the kernel's staging", c.H, c.W, c.Cin);
+    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
     int64_t m_pairs = 0;
-    int a = 4, xm = 8;
-    const int64_t grid = w43_split2_grid<TTW>(c, POOL, m_pairs, a, xm);
+    int ag = 4, xm = 8;
+    const int64_t grid = w43_split2_grid<TTW>(c, POOL, m_pairs, ag, xm);
     STITO_REQUIRE(grid > 0 && grid < (1ll << 30), STITO_E_UNSUPPORTED, "conv (two-sweep split-precision winograd): grid / cout %d", c.Cout);
+    char *ws = (char *)a.ws;
     const size_t vbytes = align_up((size_t)m_pairs * 2 * (size_t)(c.Cin / 16) * 3 * S43B_PART, 256);
-    unsigned *amax_ws = (unsigned *)(ws + vbytes);
-    const unsigned *amax = amax_in != nullptr ? amax_in : amax_ws;
     f32x4 *partial = (f32x4 *)(ws + vbytes + align_up((size_t)c.S * sizeof(unsigned), 256));
-    if (amax_in == nullptr) {   // stream maxima (not supplied by the layer that produced `in`)
-        STITO_TRY(zero_async(amax_ws, (size_t)c.S * sizeof(unsigned), st));
-        const int64_t per_stream = (int64_t)c.Cin * c.H * c.W;
-        int splits = (int)((per_stream / 4 + 256 * 16 - 1) / (256 * 16));
-        const int cap = (4096 + c.S - 1) / c.S;
-        splits = splits > cap ? cap : (splits < 1 ? 1 : splits);
-        hipLaunchKernelGGL(k_stream_absmax, dim3((unsigned)splits, (unsigned)c.S), dim3(256), 0, st, in, per_stream, amax_ws);
-        STITO_LAUNCH_CHECK();
-    }
-    {   // V slabs (MODE 4) of 2 * m_pairs pixel blocks (a block past the map transforms to zeros)
-        Wino43Geom gv = g;
-        const int n_chunks = c.Cin / W43_K;
-        const int64_t m_blocks2 = 2 * m_pairs;
-        int ncg = 1;
-        while (m_blocks2 * ncg < 1024 && n_chunks % (4 * ncg) == 0 && n_chunks / (2 * ncg) >= 4) ncg *= 2;
-        gv.n_cgroups = ncg;
-        auto kern = k_conv_wino43<TTW, POOL, false, 4>;
-        const size_t lds_t = ((size_t)2 * W43_V + 2 * W43Patch<TTW>::PFL) * sizeof(float);  // V buffers + patch buffers (no weights)
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(m_blocks2 * ncg)), dim3(W43_THREADS), lds_t, st, in, (const float *)nullptr,
-                           (const float *)amax, (const float *)nullptr, (float *)ws, gv);
-        STITO_LAUNCH_CHECK();
-    }
+    const unsigned *amax;
+    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + vbytes), amax));
+    STITO_TRY((w43_transform<TTW, POOL, 4>(g, 2 * m_pairs, a.in, amax, ws, a.st)));   // V slabs of 2 * m_pairs pixel blocks
     const bool swsplit = w43_split2_sweep_split(m_pairs, c.Cout, c.Cin);
     unsigned *flags = (unsigned *)((char *)partial + (size_t)grid * 2 * 16 * W43_THREADS * sizeof(f32x4));
     const size_t lds1 = (size_t)3 * S43B_SLAB;
     static_assert((size_t)12 * 32 * W43_XT * sizeof(float) <= (size_t)3 * S43B_SLAB, "epilogue exchange fits the slab ring");
     g.n_mblocks = (int)m_pairs;
-    g.ct_group = a;
+    g.ct_group = ag;
     g.xcd_m = xm;
-    g.amax_out = amax_out;
-    const float *u_inv = upk + (size_t)36 * c.Cout * c.Cin + 1;
+    g.amax_out = a.amax_out;
+    const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
     W43_CLK_ARM(g)
     if (swsplit) {
-        STITO_TRY(zero_async(flags, (size_t)grid * sizeof(unsigned), st));
+        STITO_TRY(zero_async(flags, (size_t)grid * sizeof(unsigned), a.st));
         auto kern = k_conv_wino43s2<TTW, POOL, true>;
         STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(2 * grid)), dim3(W43_THREADS), lds1, st, (const char *)ws, (const char *)upk, scale, shift, out, g,
-                           (const unsigned *)amax, u_inv, partial, flags);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(2 * grid)), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
+                           amax, u_inv, partial, flags);
     } else {
         auto kern = k_conv_wino43s2<TTW, POOL, false>;
         STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W43_THREADS), lds1, st, (const char *)ws, (const char *)upk, scale, shift, out, g,
-                           (const unsigned *)amax, u_inv, partial, flags);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
+                           amax, u_inv, partial, flags);
     }
     STITO_LAUNCH_CHECK();
-    W43_CLK_REPORT("k_conv_wino43s2 (f16 MFMA)", c, st)
+    W43_CLK_REPORT("k_conv_wino43s2 (f16 MFMA)", c, a.st)
     return STITO_OK;
-}
-
-int launch_wino43_split2(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                         bool pool, void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
-    const size_t need = wino43_split2_workspace_bytes(c, pool);
-    STITO_REQUIRE(need > 0 && ws != nullptr && ws_bytes >= need, STITO_E_WORKSPACE,
-                  "conv (two-sweep split-precision winograd F(4x4,3x3)): workspace have %zu need %zu", ws_bytes, need);
-    char *w = (char *)ws;
-    switch (w43_ttw(c, pool)) {
-        case 8: return pool ? launch_w43_split2<8, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split2<8, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        case 4: return pool ? launch_w43_split2<4, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split2<4, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        case 2: return pool ? launch_w43_split2<2, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split2<2, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        default: return pool ? launch_w43_split2<1, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split2<1, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-    }
 }
 
 // Six-sweep variant (k_conv_wino43s3): workspace = V slabs of the pixel-block quads | stream maxima | per-workgroup partial outputs (1 MB each).
 static int64_t w43_split3_grid_any(const ConvShape &c, bool pool, int64_t &m_quads, int &ct_group);
-bool wino43_split3_supported(const ConvShape &c, bool pool) {
+static bool wino43_split3_supported(const ConvShape &c, bool pool) {
     if (!(c.Cin % 64 == 0 && c.Cout % 512 == 0 && wino43_supported(c, pool) && ((int64_t)c.Cin * c.H * c.W) % 8 == 0)) return false;
     int64_t m_quads = 0;
     int a;
@@ -2049,16 +2001,11 @@ static int64_t w43_split3_grid(const ConvShape &c, bool pool, int64_t &m_quads, 
 
 static int64_t w43_split3_grid_any(const ConvShape &c, bool pool, int64_t &m_quads, int &ct_group) {
     int xm;
-    switch (w43_ttw(c, pool)) {
-        case 8: return w43_split3_grid<8>(c, pool, m_quads, ct_group, xm);
-        case 4: return w43_split3_grid<4>(c, pool, m_quads, ct_group, xm);
-        case 2: return w43_split3_grid<2>(c, pool, m_quads, ct_group, xm);
-        default: return w43_split3_grid<1>(c, pool, m_quads, ct_group, xm);
-    }
+    return w43_dispatch(c, pool, [&](auto ttw, auto) { return w43_split3_grid<decltype(ttw)::value>(c, pool, m_quads, ct_group, xm); });
 }
 
 // f16-pipe FLOPs the six-sweep kernel issues: pixel-block quads (padded blocks included) x 128-cout tiles x 128 x 128 x 36 x cin x 3 products
-double wino43_split3_issued_flops(const ConvShape &c, bool pool) {
+static double wino43_split3_issued_flops(const ConvShape &c, bool pool) {
     if (!wino43_split3_supported(c, pool)) return 0.0;
     int64_t m_quads = 0;
     int a;
@@ -2078,7 +2025,7 @@ int64_t wino43_split3_workgroups(const ConvShape &c, bool pool) {
 
 static size_t w43_split3_vbytes(const ConvShape &c, int64_t m_quads) { return align_up((size_t)m_quads * 6 * (size_t)(c.Cin >> 3) * S43B_PART, 256); }
 
-size_t wino43_split3_workspace_bytes(const ConvShape &c, bool pool) {
+static size_t wino43_split3_workspace_bytes(const ConvShape &c, bool pool) {
     if (!wino43_split3_supported(c, pool)) return 0;
     int64_t m_quads = 0;
     int a;
@@ -2098,102 +2045,131 @@ static bool w43_split3_sweep_split(int64_t, int) {
 }
 
 template <int TTW, bool POOL>
-static int launch_w43_split3(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                             char *ws, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
+static int launch_w43_split3(const ConvArgs &a) {
+    const ConvShape &c = a.c;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
-    STITO_REQUIRE((w43_geometry<TTW>(c, POOL, g, lds, blocks)), STITO_E_UNSUPPORTED,
-                  "conv (winograd F(4x4,3x3)): %dx%d map, %d channels does not fit the kernel's staging", c.H, c.W, c.Cin);
+    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
     int64_t m_quads = 0;
-    int a = 4, xm = 8;
-    const int64_t grid = w43_split3_grid<TTW>(c, POOL, m_quads, a, xm);
+    int ag = 4, xm = 8;
+    const int64_t grid = w43_split3_grid<TTW>(c, POOL, m_quads, ag, xm);
     STITO_REQUIRE(grid > 0 && grid < (1ll << 31), STITO_E_UNSUPPORTED, "conv (six-sweep split-precision winograd): grid / cout %d", c.Cout);
+    char *ws = (char *)a.ws;
     const size_t vbytes = w43_split3_vbytes(c, m_quads);
-    unsigned *amax_ws = (unsigned *)(ws + vbytes);
-    const unsigned *amax = amax_in != nullptr ? amax_in : amax_ws;
     f32x4 *partial = (f32x4 *)(ws + vbytes + align_up((size_t)c.S * sizeof(unsigned), 256));
-    if (amax_in == nullptr) {   // stream maxima (not supplied by the layer that produced `in`)
-        STITO_TRY(zero_async(amax_ws, (size_t)c.S * sizeof(unsigned), st));
-        const int64_t per_stream = (int64_t)c.Cin * c.H * c.W;
-        int splits = (int)((per_stream / 4 + 256 * 16 - 1) / (256 * 16));
-        const int cap = (4096 + c.S - 1) / c.S;
-        splits = splits > cap ? cap : (splits < 1 ? 1 : splits);
-        hipLaunchKernelGGL(k_stream_absmax, dim3((unsigned)splits, (unsigned)c.S), dim3(256), 0, st, in, per_stream, amax_ws);
-        STITO_LAUNCH_CHECK();
-    }
-    {   // V slabs (MODE 5) of 4 * m_quads pixel blocks (a block past the map transforms to zeros)
-        Wino43Geom gv = g;
-        const int n_chunks = c.Cin / W43_K;
-        const int64_t m_blocks4 = 4 * m_quads;
-        int ncg = 1;
-        while (m_blocks4 * ncg < 1024 && n_chunks % (4 * ncg) == 0 && n_chunks / (2 * ncg) >= 4) ncg *= 2;
-        gv.n_cgroups = ncg;
-        auto kern = k_conv_wino43<TTW, POOL, false, 5>;
-        const size_t lds_t = ((size_t)2 * W43_V + 2 * W43Patch<TTW>::PFL) * sizeof(float);  // V buffers + patch buffers (no weights)
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(m_blocks4 * ncg)), dim3(W43_THREADS), lds_t, st, in, (const float *)nullptr,
-                           (const float *)amax, (const float *)nullptr, (float *)ws, gv);
-        STITO_LAUNCH_CHECK();
-    }
+    const unsigned *amax;
+    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + vbytes), amax));
+    STITO_TRY((w43_transform<TTW, POOL, 5>(g, 4 * m_quads, a.in, amax, ws, a.st)));   // V slabs of 4 * m_quads pixel blocks
     const size_t lds1 = (size_t)3 * S43B_SLAB;
     g.n_mblocks = (int)m_quads;
-    g.ct_group = a;
+    g.ct_group = ag;
     g.xcd_m = xm;
-    g.amax_out = amax_out;
-    const float *u_inv = upk + (size_t)36 * c.Cout * c.Cin + 1;
+    g.amax_out = a.amax_out;
+    const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
     unsigned *counts = (unsigned *)((char *)partial + (size_t)grid * (8 * 2 * 4 * 20 * 64) * sizeof(f32x4));
     W43_CLK_ARM(g)
     if (w43_split3_sweep_split(m_quads, c.Cout) && 6 * grid < (1ll << 31)) {
-        STITO_TRY(zero_async(counts, (size_t)grid * sizeof(unsigned), st));
+        STITO_TRY(zero_async(counts, (size_t)grid * sizeof(unsigned), a.st));
         auto kern = k_conv_wino43s3<TTW, POOL, true>;
         STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(6 * grid)), dim3(W43_THREADS), lds1, st, (const char *)ws, (const char *)upk, scale, shift, out, g,
-                           (const unsigned *)amax, u_inv, partial, counts);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(6 * grid)), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
+                           amax, u_inv, partial, counts);
     } else {
         auto kern = k_conv_wino43s3<TTW, POOL, false>;
         STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W43_THREADS), lds1, st, (const char *)ws, (const char *)upk, scale, shift, out, g,
-                           (const unsigned *)amax, u_inv, partial, counts);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
+                           amax, u_inv, partial, counts);
     }
     STITO_LAUNCH_CHECK();
-    W43_CLK_REPORT("k_conv_wino43s3 (f16 MFMA)", c, st)
+    W43_CLK_REPORT("k_conv_wino43s3 (f16 MFMA)", c, a.st)
     return STITO_OK;
 }
 
-int launch_wino43_split3(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                         bool pool, void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
-    const size_t need = wino43_split3_workspace_bytes(c, pool);
-    STITO_REQUIRE(need > 0 && ws != nullptr && ws_bytes >= need, STITO_E_WORKSPACE,
-                  "conv (six-sweep split-precision winograd F(4x4,3x3)): workspace have %zu need %zu", ws_bytes, need);
-    char *w = (char *)ws;
-    switch (w43_ttw(c, pool)) {
-        case 8: return pool ? launch_w43_split3<8, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split3<8, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        case 4: return pool ? launch_w43_split3<4, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split3<4, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        case 2: return pool ? launch_w43_split3<2, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split3<2, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        default: return pool ? launch_w43_split3<1, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split3<1, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-    }
-}
+// ---- the algorithms of this file (conv_layout.h: ConvAlgo) ----
 
-int launch_wino43_split(const float *in, const float *upk, const float *scale, const float *shift, float *out, const ConvShape &c,
-                        bool pool, void *ws, size_t ws_bytes, hipStream_t st, const unsigned *amax_in, unsigned *amax_out) {
-    const size_t need = wino43_split_workspace_bytes(c, pool);
-    STITO_REQUIRE(need > 0 && ws != nullptr && ws_bytes >= need, STITO_E_WORKSPACE,
-                  "conv (split-precision winograd F(4x4,3x3)): workspace have %zu need %zu", ws_bytes, need);
-    char *w = (char *)ws;
-    switch (w43_ttw(c, pool)) {
-        case 8: return pool ? launch_w43_split<8, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split<8, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        case 4: return pool ? launch_w43_split<4, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split<4, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        case 2: return pool ? launch_w43_split<2, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split<2, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-        default: return pool ? launch_w43_split<1, true>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out) : launch_w43_split<1, false>(in, upk, scale, shift, out, c, w, st, amax_in, amax_out);
-    }
-}
+static size_t w43_packed_floats(int cout, int cin) { return (size_t)cout * cin * 36; }
 
-int pack_wino43(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st) {
+static int pack_wino43(const float *w_oihw, int cout, int cin, float *packed, hipStream_t st) {   // STITO_CONV_WINOGRAD_F4 and _F4_PRE
+    STITO_REQUIRE(cin % 8 == 0 && cout % 64 == 0, STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", cin, cout);
     const int64_t n = (int64_t)cout * cin;
     hipLaunchKernelGGL(k_pack_wino43, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w_oihw, cout, cin, packed);
     STITO_LAUNCH_CHECK();
     return STITO_OK;
+}
+
+// its workgroup order deals channel tiles in fours / eights
+static bool wino43_pre_supported(const ConvShape &c, bool pool) {
+    return c.Cout % 256 == 0 && (c.Cout < 1024 || c.Cout % 512 == 0) && wino43_supported(c, pool);
+}
+
+static bool wino43_split01_supported(const ConvShape &c, bool pool) {   // k_conv_wino43s / s2
+    return (c.Cout < 1024 || c.Cout % 512 == 0) && wino43_split_supported(c, pool);
+}
+
+static constexpr const char *W43S_FAMILY = "conv (split-precision winograd F(4x4,3x3))", *W43S_COVERS = "cin % 64, cout % 256";
+
+const ConvAlgo &wino43_algo() {
+    static const ConvAlgo e = {
+        .name = "conv (winograd F(4x4,3x3))", .winograd = true, .reports_amax = true, .supported = wino43_supported,
+        .packed_floats = w43_packed_floats, .pack = pack_wino43, .issued_flops = wino43_issued_flops,
+        .launch = [](const ConvArgs &a) {
+            return w43_dispatch(a.c, a.pool, [&](auto ttw, auto pool) { return launch_w43<decltype(ttw)::value, decltype(pool)::value>(a); });
+        }};
+    return e;
+}
+
+const ConvAlgo &wino43_pre_algo() {
+    static const ConvAlgo e = {
+        .name = "conv (winograd F(4x4,3x3), hoisted input transform)", .winograd = true, .reports_amax = true,
+        .same_packing = STITO_CONV_WINOGRAD_F4, .supported = wino43_pre_supported, .packed_floats = w43_packed_floats, .pack = pack_wino43,
+        .issued_flops = wino43_issued_flops, .workspace_bytes = wino43_pre_workspace_bytes, .launch = [](const ConvArgs &a) {
+            STITO_REQUIRE(a.c.Cin % 8 == 0 && a.c.Cout % 64 == 0, STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", a.c.Cin, a.c.Cout);
+            return w43_ws_launch(wino43_pre_algo(), wino43_pre_algo().name, "cout must be a multiple of 256", a, [&](auto ttw, auto pool) {
+                return launch_w43_pre<decltype(ttw)::value, decltype(pool)::value>(a);
+            });
+        }};
+    return e;
+}
+
+const ConvAlgo &wino43_split_algo() {
+    static const ConvAlgo e = {
+        .name = W43S_FAMILY, .winograd = true, .reads_amax = true, .reports_amax = true, .supported = wino43_split01_supported,
+        .packed_floats = w43s_packed_floats,
+        .pack = [](const float *w, int cout, int cin, float *packed, hipStream_t st) { return pack_wino43_split(w, cout, cin, packed, 0, st); },
+        .issued_flops = [](const ConvShape &c, bool pool) { return 3.0 * wino43_issued_flops(c, pool); },   // hi hi' + hi lo' + lo hi' on the f16 pipe
+        .workspace_bytes = wino43_split_workspace_bytes, .launch = [](const ConvArgs &a) {
+            return w43_ws_launch(wino43_split_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool) {
+                return launch_w43_split<decltype(ttw)::value, decltype(pool)::value>(a);
+            });
+        }};
+    return e;
+}
+
+const ConvAlgo &wino43_split2_algo() {
+    static const ConvAlgo e = {
+        .name = "conv (two-sweep split-precision winograd F(4x4,3x3))", .winograd = true, .reads_amax = true, .reports_amax = true,
+        .supported = wino43_split01_supported, .packed_floats = w43s_packed_floats,
+        .pack = [](const float *w, int cout, int cin, float *packed, hipStream_t st) { return pack_wino43_split(w, cout, cin, packed, 1, st); },
+        .issued_flops = wino43_split2_issued_flops, .workspace_bytes = wino43_split2_workspace_bytes, .launch = [](const ConvArgs &a) {
+            return w43_ws_launch(wino43_split2_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool) {
+                return launch_w43_split2<decltype(ttw)::value, decltype(pool)::value>(a);
+            });
+        }};
+    return e;
+}
+
+const ConvAlgo &wino43_split3_algo() {
+    static const ConvAlgo e = {
+        .name = "conv (six-sweep split-precision winograd F(4x4,3x3))", .winograd = true, .reads_amax = true, .reports_amax = true,
+        .supported = wino43_split3_supported, .packed_floats = w43s_packed_floats,
+        .pack = [](const float *w, int cout, int cin, float *packed, hipStream_t st) { return pack_wino43_split(w, cout, cin, packed, 2, st); },
+        .issued_flops = wino43_split3_issued_flops, .workspace_bytes = wino43_split3_workspace_bytes, .launch = [](const ConvArgs &a) {
+            return w43_ws_launch(wino43_split3_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool) {
+                return launch_w43_split3<decltype(ttw)::value, decltype(pool)::value>(a);
+            });
+        }};
+    return e;
 }
 
 }  // namespace stito
