@@ -367,6 +367,56 @@ size_t stito_lufs_workspace_bytes(int n_items, int64_t n_samples, int n_blocks);
 int stito_lufs(const float *audio_dev, int n_items, int channels, int64_t n_samples, const double *kweight_coef_dev,
                const int *block_lo_dev, const int *block_hi_dev, int n_blocks, double inv_block_len, float *lufs_dev,
                void *workspace_dev, size_t workspace_bytes, void *stream);
+/* ---- rule-based style transfer: run_rule_based (style_transfer.py:163-278), csrc/matcheq.hip + features.hip ---------------- */
+/* get_average_spectrum (style_transfer.py:168-181): mono mix (l + r) / 2 of a stereo item, torch.stft(n_fft, hop n_fft/4,
+ * rectangular window, centred, reflect pad, normalized=True), |X| averaged over frames -> out_dev (n_items, n_fft/2 + 1).
+ * n_fft a power of two in [2048, 32768]; n_samples > n_fft / 2.  twiddle_dev: n_fft/2 complex exp(-2 pi i k / n_fft) (float32). */
+int stito_mean_spectrum(const float *audio_dev, int n_items, int channels, int64_t n_samples, int n_fft, const float *twiddle_dev,
+                        float *out_dev, void *stream);
+/* scipy.signal.savgol_filter(row, window, polyorder) with mode "interp" (smooth_spectrum, style_transfer.py:163-165) on every row
+ * of in_dev (n_rows, n_cols) float32 -> out_dev float32, sums in float64.  coef_dev (window) doubles: savgol_coeffs in
+ * correlation order (reversed); edge_dev (window, window) doubles: row r = the polynomial fit's value at point r as weights on
+ * the window's inputs (the first / last window / 2 rows serve the two edges).  window odd, <= n_cols; not in place. */
+int stito_savgol(const float *in_dev, int n_rows, int n_cols, const double *coef_dev, int window, const double *edge_dev,
+                 float *out_dev, void *stream);
+/* scipy.signal.firwin2(n_taps, freq, gain) (style_transfer.py:235-240) per item, float64, one workgroup each.
+ *   gain = num / den in float32 with its last element set to 0 (the matched-EQ response), or num itself when den_dev is NULL;
+ *   num_dev / den_dev (n_items, n_freq) float32; freq_dev (n_freq) doubles, ascending from 0 to nyq;
+ *   grid_dev (n_grid) doubles: np.linspace(0, nyq, n_grid), n_grid = 1 + 2**ceil(log2(n_taps));
+ *   phase_b = -(n_taps - 1) / 2 * pi, inv_nyq = 1 / nyq; window_dev (n_taps) doubles (symmetric Hamming);
+ *   taps_dev (n_items, n_taps) doubles.  n_taps in [16, 4096]. */
+int stito_firwin2(const float *num_dev, const float *den_dev, int n_items, int n_freq, const double *freq_dev, const double *grid_dev,
+                  int n_grid, int n_taps, double phase_b, double inv_nyq, const double *window_dev, double *taps_dev, void *stream);
+/* scipy.signal.lfilter(taps[item], [1.0], x) on every channel (style_transfer.py:243): causal FIR, zero initial state, float64
+ * products and sums rounded to float32 once.  x_dev / y_dev (n_items, channels, n_samples), not in place; taps_dev
+ * (n_items, n_taps) doubles, n_taps <= 4096. */
+int stito_fir(const float *x_dev, int n_items, int channels, int64_t n_samples, const double *taps_dev, int n_taps, float *y_dev,
+              void *stream);
+/* In place: x = (x / d) * gain per item, d = max|x| over the item (NaN-propagating, like torch.max), clamped to clamp_min when
+ * clamp_min > 0 (a NaN peak stays NaN, like torch.clamp).  peaks_dev (n_items) float32 receives the peaks. */
+int stito_peak_normalize(float *audio_dev, int n_items, int channels, int64_t n_samples, float clamp_min, float gain,
+                         float *peaks_dev, void *stream);
+/* pyloudnorm.Meter(sr).integrated_loudness on the raw channels (style_transfer.py:250-252): like stito_lufs but without the
+ * cross-channel normalisation and with a mono item measured as one channel; kweight_coef_dev: n_items rows as stito_lufs;
+ * lufs_dev (n_items) float64, -inf for silence. */
+size_t stito_lufs_raw_workspace_bytes(int n_items, int channels, int64_t n_samples, int n_blocks);
+int stito_lufs_raw(const float *audio_dev, int n_items, int channels, int64_t n_samples, const double *kweight_coef_dev,
+                   const int *block_lo_dev, const int *block_hi_dev, int n_blocks, double inv_block_len, double *lufs_dev,
+                   void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The compressor hill-climb (style_transfer.py:254-268), every item in lockstep, state on the device: threshold_dev, delta_dev
+ * (n_items) doubles, active_dev, steps_dev (n_items) ints.  stito_climb_init: threshold 0, delta = target - input loudness,
+ * active = delta > 0.25.  stito_climb_step: for every item, Compressor(threshold, ratio 3, attack 1 ms, release 100 ms) of
+ * audio_dev into a scratch copy, x / max|x| * 10^(-12/20) in float32, raw loudness; then, for active items only, the scratch
+ * becomes audio_dev, delta = target - loudness, threshold -= 0.5, steps += 1, active = delta > 0.25 && threshold > -80.
+ * The caller loops (at most 160 steps) and may read active_dev to stop early.  Meter arguments as stito_lufs_raw. */
+int stito_climb_init(const double *input_lufs_dev, const double *target_lufs_dev, int n_items, double *threshold_dev,
+                     double *delta_dev, int *active_dev, int *steps_dev, void *stream);
+size_t stito_climb_workspace_bytes(int n_items, int channels, int64_t n_samples, int n_blocks);
+int stito_climb_step(float *audio_dev, int n_items, int channels, int64_t n_samples, double sample_rate,
+                     const double *kweight_coef_dev, const int *block_lo_dev, const int *block_hi_dev, int n_blocks,
+                     double inv_block_len, const double *target_lufs_dev, double *threshold_dev, double *delta_dev,
+                     int *active_dev, int *steps_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* compute_barkspectrum (features.py:166-232).  mode 0 mono / 1 stereo / 2 mid-side; fft_size a power of two
  * <= 32768 (hop fft_size/4, rectangular window, centred, reflect pad); twiddle_dev: fft_size/2 complex
  * exp(-2 pi i k / fft_size); fb_dev (n_bands, fft_size/2 + 1): barkscale_fbanks transposed;

@@ -21,6 +21,7 @@
 //   distortion/gain: element-wise.
 #include "common.h"
 #include "dsp_view.h"
+#include "juce_comp.h"
 
 namespace stito {
 
@@ -62,11 +63,6 @@ struct ChainArgs {
     int n_fx;
     stito_fx_desc fx[16];
 };
-
-// juce::Decibels::decibelsToGain<float>
-__device__ __forceinline__ float db_to_gain(float db, float minus_inf) {
-    return db > minus_inf ? powf(10.0f, db * 0.05f) : 0.0f;
-}
 
 // RBJ biquad, effects.py:395-450.  kind: 0 low-shelf, 1 peaking, 2 high-shelf.
 __device__ void rbj(double gain_db, double f, double q, double sr, int kind, double *o /*b0 b1 b2 a1 a2*/) {
@@ -120,18 +116,8 @@ __global__ void k_prepare(ChainArgs chain, const double *__restrict__ w, int P, 
     double *o = coef + ((int64_t)f * P + cand) * COEF_STRIDE;
     if (kind == STITO_FX_PARAMETRIC_EQ) {
         for (int s = 0; s < 6; ++s) rbj(v[3 * s], v[3 * s + 1], v[3 * s + 2], sr, s == 0 ? 0 : (s == 5 ? 2 : 1), o + 5 * s);
-    } else if (kind == STITO_FX_COMPRESSOR) {  // juce::dsp::Compressor<float>::update + BallisticsFilter
-        const float thr = db_to_gain((float)v[0], -200.0f);
-        const float expf_ = (float)(-2.0 * M_PI * 1000.0 / sr);
-        const float at = (float)v[2], rl = (float)v[3];
-        o[0] = thr;
-        o[1] = 1.0f / thr;
-        o[2] = 1.0f / (float)v[1] - 1.0f;
-        // the one-pole coefficients sit next to 1 and the envelope only sees 1 - c: one ulp of c is up to 3e-5 of
-        // (1 - c).  exp in double of the float32 argument, rounded once, is the correctly rounded expf the host libm
-        // returns (ocml's expf is allowed 1 ulp)
-        o[3] = at < 1.0e-3f ? 0.0f : (float)exp((double)(expf_ / at));
-        o[4] = rl < 1.0e-3f ? 0.0f : (float)exp((double)(expf_ / rl));
+    } else if (kind == STITO_FX_COMPRESSOR) {  // juce::dsp::Compressor<float>::update + BallisticsFilter (juce_comp.h)
+        juce_compressor_coef(v[0], v[1], v[2], v[3], sr, o);
     } else if (kind == STITO_FX_DISTORTION) {
         o[0] = db_to_gain((float)v[0], -100.0f);
         o[1] = db_to_gain((float)v[1], -100.0f);

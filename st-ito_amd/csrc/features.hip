@@ -7,6 +7,8 @@
 //   compute_rms_energy         features.py:235-245
 //   compute_crest_factor       features.py:248-264 (including its per-sample cross-channel "peak normalise")
 //   compute_spectral_centroid  features.py:302-333 -> torchaudio SpectralCentroid(n_fft 2048, hop 1024, Hann)
+//   get_average_spectrum       style_transfer.py:168-181 (run_rule_based): the same STFT, mean over frames of |X| per bin
+//   the meter of run_rule_based style_transfer.py:243-245: pyloudnorm on the raw channels (stito_lufs_raw)
 //
 // One workgroup per (item, signal) walks the frames of its signal: n_fft real samples are packed as
 // n_fft/2 complex points and transformed IN PLACE in LDS (radix-2 decimation in frequency, 128 KB
@@ -68,6 +70,7 @@ __device__ __forceinline__ float ft_mag(const float2 *z, const float2 *__restric
 
 // MODE 0: bark spectrum -> out (item, n_bands, n_sig) = log(fb . mean_t |X| + 1e-8)
 // MODE 1: spectral centroid per frame -> out (item * n_sig, T)
+// MODE 2: mean magnitude spectrum -> out (item * n_sig, n_fft/2 + 1) = nyq_step * mean_t |X|  (nyq_step: the caller's scale)
 template <int NT, int MODE>
 __global__ __launch_bounds__(NT) void k_stft_feature(const float *__restrict__ audio, int C, int64_t L, int mode, int n_sig,
                                                       int log2n2, int hop, int64_t T, const float *__restrict__ window,
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(NT) void k_stft_feature(const float *__restrict__ a
         }
         __syncthreads();
         ft_fft_dif<NT>(z, tw, log2n2, tid);
-        if (MODE == 0) {
+        if (MODE != 1) {
 #pragma unroll
             for (int u = 0; u < MAXB - 1; ++u) {
                 const int k = tid + u * NT;
@@ -122,6 +125,16 @@ __global__ __launch_bounds__(NT) void k_stft_feature(const float *__restrict__ a
             }
         }
         __syncthreads();  // z is rewritten by the next frame
+    }
+    if (MODE == 2) {
+        // torch's X.abs().mean(-1) of the normalised transform: the sum over frames / T, then the scale
+        float *o = out + (int64_t)blockIdx.x * (N2 + 1);
+#pragma unroll
+        for (int u = 0; u < MAXB - 1; ++u) {
+            const int k = tid + u * NT;
+            if (k < N2) o[k] = acc[u] / (float)T * nyq_step;
+        }
+        if (tid == 0) o[N2] = acc[MAXB - 1] / (float)T * nyq_step;
     }
     if (MODE == 0) {
         // mean over frames -> LDS (float view of z), then one filterbank row per wave at a time
@@ -335,29 +348,43 @@ __global__ __launch_bounds__(256) void k_lufs_blocks(const float *__restrict__ y
     __syncthreads();
     if (tid == 0) z[(int64_t)sc * n_blocks + j] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_len;
 }
-// (4) gating: absolute -70 LUFS, relative -10 LU below the absolutely-gated mean; one thread per item (channel gains 1, 1)
-__global__ void k_lufs_gate(const double *__restrict__ z, int n_items, int n_blocks, float *__restrict__ lufs) {
-    const int item = blockIdx.x * blockDim.x + threadIdx.x;
-    if (item >= n_items) return;
-    const double *z0 = z + (int64_t)item * 2 * n_blocks, *z1 = z0 + n_blocks;
+// (4) gating: absolute -70 LUFS, relative -10 LU below the absolutely-gated mean (channel gains 1, 1); z1 == nullptr: one
+// channel (adding 0.0 in its place is exact)
+__device__ double lufs_gate(const double *__restrict__ z0, const double *__restrict__ z1, int n_blocks) {
     double s0 = 0.0, s1 = 0.0;
     int cnt = 0;
     for (int j = 0; j < n_blocks; ++j) {
-        const double l = -0.691 + 10.0 * log10(z0[j] + z1[j]);
-        if (l >= -70.0) { s0 += z0[j]; s1 += z1[j]; ++cnt; }
+        const double l = -0.691 + 10.0 * log10(z0[j] + (z1 ? z1[j] : 0.0));
+        if (l >= -70.0) { s0 += z0[j]; s1 += z1 ? z1[j] : 0.0; ++cnt; }
     }
-    float out = -INFINITY;
+    double out = -INFINITY;
     if (cnt > 0) {
         const double gamma_r = -0.691 + 10.0 * log10(s0 / cnt + s1 / cnt) - 10.0;
         s0 = s1 = 0.0;
         cnt = 0;
         for (int j = 0; j < n_blocks; ++j) {
-            const double l = -0.691 + 10.0 * log10(z0[j] + z1[j]);
-            if (l > gamma_r && l > -70.0) { s0 += z0[j]; s1 += z1[j]; ++cnt; }
+            const double l = -0.691 + 10.0 * log10(z0[j] + (z1 ? z1[j] : 0.0));
+            if (l > gamma_r && l > -70.0) { s0 += z0[j]; s1 += z1 ? z1[j] : 0.0; ++cnt; }
         }
-        if (cnt > 0) out = (float)(-0.691 + 10.0 * log10(s0 / cnt + s1 / cnt));
+        if (cnt > 0) out = -0.691 + 10.0 * log10(s0 / cnt + s1 / cnt);
     }
-    lufs[item] = out;
+    return out;
+}
+
+// one thread per item; z (n, 2, n_blocks)
+__global__ void k_lufs_gate(const double *__restrict__ z, int n_items, int n_blocks, float *__restrict__ lufs) {
+    const int item = blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= n_items) return;
+    const double *z0 = z + (int64_t)item * 2 * n_blocks;
+    lufs[item] = (float)lufs_gate(z0, z0 + n_blocks, n_blocks);
+}
+
+// pyloudnorm's meter on the raw channels (no cross-channel normalisation, a mono item measured as one channel): z (n, C, n_blocks)
+__global__ void k_lufs_gate_raw(const double *__restrict__ z, int n_items, int C, int n_blocks, double *__restrict__ lufs) {
+    const int item = blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= n_items) return;
+    const double *z0 = z + (int64_t)item * C * n_blocks;
+    lufs[item] = lufs_gate(z0, C == 2 ? z0 + n_blocks : nullptr, n_blocks);
 }
 
 extern "C" size_t stito_lufs_workspace_bytes(int n_items, int64_t n_samples, int n_blocks) {
@@ -386,6 +413,57 @@ extern "C" int stito_lufs(const float *audio_dev, int n_items, int channels, int
                        n_blocks, inv_block_len, z);
     STITO_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_lufs_gate, dim3((n_items + 63) / 64), dim3(64), 0, st, (const double *)z, n_items, n_blocks, lufs_dev);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
+extern "C" size_t stito_lufs_raw_workspace_bytes(int n_items, int channels, int64_t n_samples, int n_blocks) {
+    if (n_items <= 0 || channels <= 0 || n_samples <= 0 || n_blocks <= 0) return 0;
+    return align_up((size_t)n_items * channels * n_samples * sizeof(float), 256) +
+           align_up((size_t)n_items * channels * n_blocks * sizeof(double), 256);
+}
+
+extern "C" int stito_lufs_raw(const float *audio_dev, int n_items, int channels, int64_t n_samples, const double *kweight_coef_dev,
+                              const int *block_lo_dev, const int *block_hi_dev, int n_blocks, double inv_block_len, double *lufs_dev,
+                              void *workspace_dev, size_t workspace_bytes, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    STITO_REQUIRE(n_items > 0 && n_samples > 0 && n_blocks > 0, STITO_E_INVALID, "stito_lufs_raw: empty input");
+    STITO_REQUIRE(channels == 1 || channels == 2, STITO_E_INVALID, "Invalid number of channels: %d", channels);
+    STITO_REQUIRE(n_samples < (1ll << 31), STITO_E_UNSUPPORTED, "stito_lufs_raw: %lld samples", (long long)n_samples);
+    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= stito_lufs_raw_workspace_bytes(n_items, channels, n_samples, n_blocks),
+                  STITO_E_WORKSPACE, "stito_lufs_raw: workspace too small");
+    float *y = (float *)workspace_dev;
+    double *z = (double *)((char *)workspace_dev + align_up((size_t)n_items * channels * n_samples * sizeof(float), 256));
+    InView in{audio_dev, (int64_t)channels * n_samples, n_samples, channels};
+    STITO_TRY(eq_cascade(in, y, n_items, channels, n_samples, kweight_coef_dev, st));
+    hipLaunchKernelGGL(k_lufs_blocks, dim3(n_blocks, n_items * channels), dim3(256), 0, st, (const float *)y, n_samples, block_lo_dev,
+                       block_hi_dev, n_blocks, inv_block_len, z);
+    STITO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_lufs_gate_raw, dim3((n_items + 63) / 64), dim3(64), 0, st, (const double *)z, n_items, channels, n_blocks, lufs_dev);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
+extern "C" int stito_mean_spectrum(const float *audio_dev, int n_items, int channels, int64_t n_samples, int n_fft,
+                                   const float *twiddle_dev, float *out_dev, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int l2 = feat_log2(n_fft);
+    STITO_REQUIRE(l2 >= 11 && l2 <= 15, STITO_E_UNSUPPORTED, "mean spectrum: n_fft %d must be a power of two in [2048, 32768]", n_fft);
+    STITO_REQUIRE(n_items > 0, STITO_E_INVALID, "stito_mean_spectrum: empty input");
+    STITO_REQUIRE(channels == 1 || channels == 2, STITO_E_INVALID, "Invalid number of channels: %d", channels);
+    STITO_REQUIRE(n_samples > n_fft / 2, STITO_E_INVALID, "reflect padding needs n_samples > n_fft/2");
+    const int hop = n_fft / 4;
+    const int64_t T = n_samples / hop + 1;
+    const size_t lds = (size_t)(n_fft / 2 + 8) * sizeof(float2);
+    const float scale = (float)(1.0 / sqrt((double)n_fft));  // torch.stft(normalized=True)
+    if (n_fft >= 4096) {
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_stft_feature<1024, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_stft_feature<1024, 2>), dim3(n_items), dim3(1024), lds, st, audio_dev, channels, n_samples, (int)FEAT_MONO, 1,
+                           l2 - 1, hop, T, nullptr, (const float2 *)twiddle_dev, nullptr, 0, scale, out_dev);
+    } else {
+        hipLaunchKernelGGL((k_stft_feature<256, 2>), dim3(n_items), dim3(256), lds, st, audio_dev, channels, n_samples, (int)FEAT_MONO, 1,
+                           l2 - 1, hop, T, nullptr, (const float2 *)twiddle_dev, nullptr, 0, scale, out_dev);
+    }
     STITO_LAUNCH_CHECK();
     return STITO_OK;
 }

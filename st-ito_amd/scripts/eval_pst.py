@@ -3,14 +3,16 @@
 scripts/eval/eval_pst.py (get_plugins 206-650 for the pedalboard chains, run_pst_benchmark 652-903,
 method settings 974-991: popsize 128, 32 iterations, sigma0 0.33, find_w0 False, random_crop True).
 
-Differences, all stated: only the `*-pb` chains (Basic* effects) and the `style-es` method are
-built -- the VST chains need binary plugins and the other methods (random, rule-based, DeepAFx-ST)
-other models.  The examples come from `--pairs file` (one "input.wav<TAB>target.wav" per line,
+Differences, all stated: only the `*-pb` chains (Basic* effects) are built -- the VST chains need
+binary plugins.  Of the methods (945-991) `input`, `random`, `rule-based` and `style-es` are built
+(`--methods`, default `input style-es`); DeepAFx-ST needs a trained checkpoint and its package, which
+do not exist here.  The examples come from `--pairs file` (one "input.wav<TAB>target.wav" per line,
 relative to --root-dir) or `--synthetic N`; the reference's hard-coded file lists are its own
 dataset and are not reproduced.  With `--batched` all examples of equal length are optimised together
 by run_es_batch (BASELINE.json configs[2]) instead of one after the other.
 
     python st-ito_amd/scripts/eval_pst.py --chain general-pb --synthetic 4 --max-iters 8 --popsize 32
+    python st-ito_amd/scripts/eval_pst.py --chain general-pb --synthetic 2 --methods input random rule-based style-es
 """
 from __future__ import annotations
 
@@ -79,39 +81,68 @@ def style_distance(a: torch.Tensor, b: torch.Tensor, model, sr: int) -> float:
     return float(torch.stack([torch.cosine_similarity(ea[k], eb[k], dim=1) for k in ea]).mean())
 
 
+# --methods choice -> the reference's result key (eval_pst.py:945-991)
+METHODS = OrderedDict([("input", "input"), ("random", "random"), ("rule-based", "rule-based"), ("style-es", "style-es (param-panns)")])
+DEFAULT_METHODS = ("input", "style-es")
+
+
 def run_pst_benchmark(pairs, plugins, model, out_dir: str, max_iters: int = 32, popsize: int = 128, sigma0: float = 0.33,
-                      random_crop: bool = True, seed: int = None, batched: bool = False, tag: str = "pb"):
+                      random_crop: bool = True, seed: int = None, batched: bool = False, tag: str = "pb",
+                      methods=DEFAULT_METHODS):
     """pairs: list of (name, input (chs, n), input_sr, target (chs, n), target_sr).  Returns the results dict
-    the reference dumps to JSON: per method, per metric, one value per example (+ time_elapsed)."""
+    the reference dumps to JSON: per method, per metric, one value per example (+ time_elapsed).
+
+    methods: any of "input", "random", "rule-based", "style-es" (results in that order, under the reference's keys).  Every
+    method gets clones of the prepared pair; its time_elapsed is the wall time of its call, like the reference's (757-763;
+    the input arm records 0).  Like the reference, only a method that returns "params" (the ES) writes a .json."""
     from st_ito.audio_io import save_wav
     from st_ito.loudness import normalize_loudness
-    from st_ito.style_transfer import load_plugins, run_es, run_es_batch
+    from st_ito.style_transfer import load_plugins, run_es, run_es_batch, run_random, run_rule_based
     from st_ito.utils import get_param_embeds
 
+    for m in methods:
+        if m in ("deepafx-st", "deepafx-st+"):
+            raise NotImplementedError(f"method {m!r} needs a trained DeepAFx-ST checkpoint and its package; not built here")
+        if m not in METHODS:
+            raise ValueError(f"Unknown method {m!r}: choose from {list(METHODS)}")
+    methods = [m for m in METHODS if m in methods]
     os.makedirs(out_dir, exist_ok=True)
     plugins, _, _ = load_plugins(plugins)
     sr = 48000
     prepared = [(name,) + prepare_pair(x, xsr, t, tsr) for name, x, xsr, t, tsr in pairs]
-    results = {m: {"time_elapsed": [], "style_features": []} for m in ("input", "style-es (param-panns)")}
+    results = {METHODS[m]: {"time_elapsed": [], "style_features": []} for m in methods}
+
+    def timed(fn, *a, **k):
+        t0 = time.time()
+        r = fn(*a, **k)
+        return r, time.time() - t0
 
     es_out = [None] * len(prepared)
-    if batched and len({(p[1].shape, p[2].shape) for p in prepared}) == 1 and prepared[0][1].shape == prepared[0][2].shape:
+    if "style-es" in methods and batched and len({(p[1].shape, p[2].shape) for p in prepared}) == 1 and prepared[0][1].shape == prepared[0][2].shape:
         t0 = time.time()
         res = run_es_batch(torch.cat([p[1] for p in prepared]), torch.cat([p[2] for p in prepared]), sr, plugins, model,
                            get_param_embeds, max_iters=max_iters, sigma0=sigma0, popsize=popsize, random_crop=random_crop, seed=seed)
         dt = (time.time() - t0) / len(prepared)
         es_out = [(r, dt) for r in res]
     for idx, (name, xin, tgt, min_len) in enumerate(prepared):
-        if es_out[idx] is None:
-            t0 = time.time()
-            r = run_es(xin.clone(), tgt.clone(), sr, plugins, model, get_param_embeds, max_iters=max_iters, sigma0=sigma0,
-                       popsize=popsize, find_w0=False, random_crop=random_crop, distance="cosine", dropout=0.0,
-                       seed=None if seed is None else seed + idx)
-            es_out[idx] = (r, time.time() - t0)
-        for method, (out_audio, elapsed, params) in {
-            "input": (xin[0], 0.0, None),
-            "style-es (param-panns)": (es_out[idx][0]["output_audio"], es_out[idx][1], es_out[idx][0]["params"]),
-        }.items():
+        outs = OrderedDict()
+        for m in methods:
+            if m == "input":
+                outs[m] = (xin[0], 0.0, None)
+            elif m == "random":
+                r, dt = timed(run_random, xin.clone(), tgt.clone(), sr, plugins, None)
+                outs[m] = (r["output_audio"][0], dt, None)
+            elif m == "rule-based":
+                r, dt = timed(run_rule_based, xin.clone(), tgt.clone(), sr, plugins, None)
+                outs[m] = (r["output_audio"][0], dt, None)
+            else:
+                if es_out[idx] is None:
+                    es_out[idx] = timed(run_es, xin.clone(), tgt.clone(), sr, plugins, model, get_param_embeds, max_iters=max_iters,
+                                        sigma0=sigma0, popsize=popsize, find_w0=False, random_crop=random_crop, distance="cosine",
+                                        dropout=0.0, seed=None if seed is None else seed + idx)
+                outs[m] = (es_out[idx][0]["output_audio"], es_out[idx][1], es_out[idx][0]["params"])
+        for m, (out_audio, elapsed, params) in outs.items():
+            method = METHODS[m]
             results[method]["time_elapsed"].append(elapsed)
             results[method]["style_features"].append(style_distance(out_audio[None], tgt, model, sr))
             stem = f"{idx:02d}_{method.split(' ')[0]}_{tag}"
@@ -161,6 +192,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--batched", action="store_true")
     ap.add_argument("--ckpt", default=None, help="AFx-Rep checkpoint; omitted: seeded random weights")
+    ap.add_argument("--methods", nargs="+", default=list(DEFAULT_METHODS), choices=list(METHODS) + ["deepafx-st"],
+                    help="methods to run (deepafx-st: not built, raises)")
     ap.add_argument("--output-dir", default=os.path.join("output", "pst"))
     a = ap.parse_args(argv)
 
@@ -181,7 +214,7 @@ def main(argv=None):
     else:
         ap.error("give --pairs or --synthetic N")
     return run_pst_benchmark(pairs, plugins, model, os.path.join(a.output_dir, a.chain), a.max_iters, a.popsize,
-                             seed=a.seed, batched=a.batched, tag=a.chain)
+                             seed=a.seed, batched=a.batched, tag=a.chain, methods=a.methods)
 
 
 if __name__ == "__main__":

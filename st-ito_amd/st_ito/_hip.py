@@ -120,6 +120,19 @@ SIGNATURES = {
     "stito_resample_num_samples": (c_int64, [c_int64, c_int, c_int]),
     "stito_resample_sinc": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "stito_neg_cosine": (c_int, [c_void_p, c_int, c_int, c_void_p, ctypes.c_float, c_int, c_void_p, c_void_p]),
+    "stito_mean_spectrum": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "stito_savgol": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "stito_firwin2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p,
+                              c_void_p, c_void_p]),
+    "stito_fir": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "stito_peak_normalize": (c_int, [c_void_p, c_int, c_int, c_int64, c_float, c_float, c_void_p, c_void_p]),
+    "stito_lufs_raw_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int]),
+    "stito_lufs_raw": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
+    "stito_climb_init": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "stito_climb_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int]),
+    "stito_climb_step": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

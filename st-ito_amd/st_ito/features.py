@@ -137,11 +137,26 @@ def compute_lufs(x: torch.Tensor, sample_rate: float, **kwargs):
     """(bs, 1) -- reference features.py:267-299: per-sample cross-channel normalisation, mono duplicated, integrated
     loudness (pyloudnorm there; the same BS.1770-4 measurement on the GPU here: stito_lufs -- K-weighting through the
     effect chain's float64 biquad cascade, gated block energies in float64; st_ito.loudness is its host restatement)."""
-    from .loudness import _k_weighting
-
     xin, dev = _gpu(x)
     bs, chs, n = xin.shape
     sr = float(sample_rate)
+    T_g = 0.400
+    row, lo, hi, n_blocks = _lufs_tables(n, sr, dev)
+    coef = row[None, :].repeat(bs, 1).contiguous()
+    L = _hip.lib()
+    ws = torch.empty(L.stito_lufs_workspace_bytes(bs, n, n_blocks), dtype=torch.uint8, device=dev)
+    out = torch.empty((bs, 1), dtype=torch.float32, device=dev)
+    _hip.check(L.stito_lufs(_hip.ptr(xin), bs, chs, n, _hip.ptr(coef), _hip.ptr(lo), _hip.ptr(hi), n_blocks, 1.0 / (T_g * sr),
+                            _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
+    return out.to(x.device).type_as(x)
+
+
+def _lufs_tables(n: int, sr: float, dev):
+    """The meter's device tables for n samples at sr (pyloudnorm's 400 ms blocks at 75 % overlap): the K-weighting row
+    (32 doubles: the two biquads, then identity sections), block edges lo / hi (int32, the library's int() of float
+    products) and the block count.  Raises like the meter when n is shorter than one block."""
+    from .loudness import _k_weighting
+
     T_g, step = 0.400, 0.25
     if n < T_g * sr:
         raise ValueError("Audio must have length greater than the block size.")
@@ -156,14 +171,7 @@ def compute_lufs(x: torch.Tensor, sample_rate: float, **kwargs):
         hi = np.array([int(T_g * (j * step + 1) * sr) for j in range(n_blocks)], dtype=np.int32)
         hi = np.minimum(hi, n)
         _cache[key] = (torch.from_numpy(row).to(dev), torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev), n_blocks)
-    row, lo, hi, n_blocks = _cache[key]
-    coef = row[None, :].repeat(bs, 1).contiguous()
-    L = _hip.lib()
-    ws = torch.empty(L.stito_lufs_workspace_bytes(bs, n, n_blocks), dtype=torch.uint8, device=dev)
-    out = torch.empty((bs, 1), dtype=torch.float32, device=dev)
-    _hip.check(L.stito_lufs(_hip.ptr(xin), bs, chs, n, _hip.ptr(coef), _hip.ptr(lo), _hip.ptr(hi), n_blocks, 1.0 / (T_g * sr),
-                            _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
-    return out.to(x.device).type_as(x)
+    return _cache[key]
 
 
 def compute_spectral_centroid(x: torch.Tensor, sample_rate: float, *args, **kwargs):

@@ -3,10 +3,12 @@
 and `run_es` (399-692), with the evaluate-population step on the MI355X; `run_staged_es` is the fixed variant
 of scripts/run_optim.py:39-234 on the same evaluate step.
 
-Only the ES path is built; the baselines of the reference file (run_input, run_random,
-run_rule_based, run_deepafx_st) are outside this build's scope.  `run_es_batch` is an extension
-(BASELINE.json configs[2]): several (input, target) pairs optimised together, every iteration
-evaluating all their populations in one GPU batch.
+The baselines of the production-style-transfer benchmark are built too: `run_input` (116-135), `run_random` (138-160:
+one random parameter vector through the GPU render) and `run_rule_based` (163-278: matched-EQ design and FIR filtering,
+then a compressor threshold hill-climb, every item of the batch at once on the GPU -- csrc/matcheq.hip, st_ito.matcheq),
+with the reference's `get_average_spectrum` and `smooth_spectrum`.  `run_deepafx_st` is not: it needs a trained
+DeepAFx-ST checkpoint and its package.  `run_es_batch` is an extension (BASELINE.json configs[2]): several (input,
+target) pairs optimised together, every iteration evaluating all their populations in one GPU batch.
 """
 from __future__ import annotations
 
@@ -118,6 +120,117 @@ def savepop_to_disk(iteration, fvals, output_embeds, output_audios, run_dir: str
         audio = output_audios[i - first]
         audio = audio / torch.max(torch.abs(audio)).clamp(min=1e-8)
         save_wav(os.path.join(pop_dir, f"output_audio_pop_{idx}_fval_{fvals[i]:0.4e}.wav"), audio.cpu(), sample_rate)
+
+
+# ------ baselines of the PST benchmark ------
+def run_input(input_audio: torch.Tensor, target_audio: torch.Tensor, sample_rate: int, plugins: List[dict], model: torch.nn.Module,
+              *args, **kwargs):
+    """The unprocessed input (reference style_transfer.py:121-135)."""
+    bs, chs, seq_len = input_audio.shape
+    return {"output_audio": input_audio}
+
+
+def run_random(input_audio: torch.Tensor, target_audio: torch.Tensor, sample_rate: int, plugins: List[dict], model: torch.nn.Module,
+               *args, **kwargs):
+    """One random parameter vector (reference style_transfer.py:138-160): w = torch.rand(total_num_params) from torch's global
+    CPU generator, rendered by process_audio on the GPU.  input_audio (1, chs, seq_len)."""
+    bs, chs, seq_len = input_audio.shape
+    total_num_params = sum([plugin["num_params"] for plugin in plugins.values()])
+    w = torch.rand(total_num_params)
+    output_audio = process_audio(input_audio.squeeze(0), w.numpy(), sample_rate, plugins)
+    output_audio = torch.from_numpy(output_audio).unsqueeze(0)
+    return {"output_audio": output_audio, "param_dict": parameters_to_dict(w.numpy(), plugins)}
+
+
+def smooth_spectrum(H):
+    """scipy.signal.savgol_filter(H, 1025, 2) (reference style_transfer.py:163-165) of a spectrum or a (rows, bins) stack, on the
+    GPU (float64 sums, float32 result).  A numpy array comes back as a numpy array, a tensor as a tensor on its device."""
+    from . import matcheq
+
+    as_numpy = not isinstance(H, torch.Tensor)
+    h = torch.as_tensor(np.asarray(H) if as_numpy else H)
+    dev = h.device if h.is_cuda else _gpu_device()
+    rows = h.detach().to(dev, torch.float32).reshape(-1, h.shape[-1]).contiguous()
+    out = matcheq.savgol(rows).reshape(h.shape)
+    return out.cpu().numpy() if as_numpy else out.to(h.device)
+
+
+def get_average_spectrum(x: torch.Tensor, n_fft: int = 16384):
+    """Mean over STFT frames of |X| (reference style_transfer.py:168-181): x (chs, seq_len), a stereo signal averaged to mono
+    first; torch.stft(n_fft, hop n_fft // 4, rectangular window, centred, reflect pad, normalized=True).  Prints x.shape like
+    the reference.  -> (n_fft // 2 + 1,) float32 on x's device, computed on the GPU."""
+    from . import matcheq
+
+    print(x.shape)
+    _check_rule_based_shape(x[None], n_fft, None, "x")
+    dev = x.device if x.is_cuda else _gpu_device()
+    xs = x.detach().to(dev, torch.float32)[None].contiguous()
+    return matcheq.mean_spectrum(xs, n_fft)[0].to(x.device)
+
+
+def _gpu_device():
+    from . import _hip
+
+    _hip.require_gpu()
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _check_rule_based_shape(x: torch.Tensor, n_fft: int, sample_rate, name: str):
+    """The shapes run_rule_based can process: (bs, 1 or 2, n) with n > n_fft / 2 (reflect padding) and, for the loudness meter,
+    n >= 0.4 s."""
+    if x.dim() != 3:
+        raise ValueError(f"{name}: expected (bs, chs, seq_len), got {tuple(x.shape)}")
+    bs, chs, n = x.shape
+    if chs not in (1, 2):
+        raise ValueError(f"{name}: {chs} channels; the matched EQ is defined for mono or stereo audio")
+    if n_fft & (n_fft - 1) or not 2048 <= n_fft <= 32768:
+        raise NotImplementedError(f"n_fft {n_fft}: only powers of two in [2048, 32768] are built")
+    if n <= n_fft // 2:
+        raise ValueError(f"{name}: {n} samples; reflect padding needs more than n_fft // 2 = {n_fft // 2}")
+    if sample_rate is not None and n < 0.400 * sample_rate:
+        raise ValueError(f"{name}: {n} samples are shorter than the loudness meter's 400 ms block")
+
+
+def run_rule_based(input_audio: torch.Tensor, target_audio: torch.Tensor, sample_rate: int, plugins: List[dict],
+                   model: torch.nn.Module, n_fft: int = 16384, n_taps: int = 2048, **kwargs):
+    """Rule-based style transfer baseline (reference style_transfer.py:184-278): per item, a matched EQ -- the ratio of the
+    target's and the input's smoothed average spectra, designed as an n_taps linear-phase FIR by firwin2 and applied to every
+    channel -- then a compressor (ratio 3, attack 1 ms, release 100 ms) whose threshold walks down from 0 dB in 0.5 dB steps,
+    each pass compressing the previous pass's output, until the output is within 0.25 LU of the target's loudness or the
+    threshold reaches -80 dB.
+
+    Like the reference, every item of input_audio and target_audio is peak-normalised to -12 dBFS IN PLACE first.  From
+    there the audio stays on the GPU and all items run together (the hill-climb in lockstep, each item with its own
+    threshold and stopping step).  plugins and model are not used.  -> {"output_audio": (bs, chs, seq_len) float32 CPU}."""
+    from . import matcheq
+
+    _check_rule_based_shape(input_audio, n_fft, sample_rate, "input_audio")
+    _check_rule_based_shape(target_audio, n_fft, sample_rate, "target_audio")
+    bs = input_audio.shape[0]
+    if target_audio.shape[0] != bs:
+        raise ValueError(f"input_audio has {bs} items, target_audio {target_audio.shape[0]}")
+    if not 16 <= n_taps <= 4096:
+        raise NotImplementedError(f"n_taps {n_taps}: only 16 .. 4096 are built")
+    dev = _gpu_device()
+
+    def normalised(a):  # peak normalise to -12 dBFS on the GPU, then write back into the caller's tensor
+        g = matcheq.peak_normalize_(a.detach().to(dev, torch.float32).contiguous())
+        if g.data_ptr() != a.data_ptr():
+            with torch.no_grad():
+                a.copy_(g)
+        return g
+
+    xs, ts = normalised(input_audio), normalised(target_audio)
+    for b in range(bs):  # get_average_spectrum prints the shape of every signal it is given
+        print(input_audio[b].shape)
+        print(target_audio[b].shape)
+    # ------------ design the matched EQ ------------
+    sm = matcheq.savgol(torch.cat([matcheq.mean_spectrum(ts, n_fft), matcheq.mean_spectrum(xs, n_fft)]))
+    taps = matcheq.firwin2(sm[:bs].contiguous(), sm[bs:].contiguous(), sample_rate, n_taps)
+    y = matcheq.peak_normalize_(matcheq.fir(xs, taps))
+    # ------------ dynamics: the threshold hill-climb ------------
+    matcheq.hill_climb_(y, matcheq.lufs_raw(y, sample_rate), matcheq.lufs_raw(ts, sample_rate), sample_rate)
+    return {"output_audio": y.cpu()}
 
 
 # ----------- Evolutionary Strategies ------------
