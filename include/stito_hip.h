@@ -90,6 +90,9 @@ const char *stito_last_error(void);
  * 9: algorithms 6 and 7 and stito_conv_block1_fused / stito_cnn14_pack_conv1_fused retired;
  * STITO_CONV_WINOGRAD_F4_SPLIT3; 10: stito_cnn14_weights.chunk_* (appended), stito_conv_timing_read_tagged). */
 int stito_version(void);
+/* Additions since the last change of stito_version() that leave every existing symbol and struct as it is (a caller built against
+ * 10.0 runs unchanged): 1 = stito_gather_crops. */
+int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
  * rate / fs per sample, wrapped), n < n_samples.  The recurrence is walked on the host and copied (this call BLOCKS on `stream`
@@ -438,6 +441,21 @@ int stito_spectral_centroid(const float *audio_dev, int n_items, int channels, i
  * [mean | std | max], rows L2-normalised.  n_mfcc <= 32; any number of frames T >= 2. */
 int stito_mfcc_stats(const float *logmel_dev, int n_items, int channels, int64_t n_frames, int n_mels,
                      const float *dct_dev, int n_mfcc, float top_db, float *out_dev, void *stream);
+
+/* ---- ragged multi-pair batches (ABI 10.1; an extension like stito_render_population_multi) ---- */
+/* The evaluate-time inputs of pairs whose files differ in length (style_transfer.py:505-518: crop to, or zero-pad to, 262144 samples),
+ * cut in ONE launch out of a buffer that holds every input once:
+ *   packed_dev  (packed_floats) float32: input b is (channels, length[b]) row-major at packed_dev + offset[b]
+ *   offset_dev, length_dev, start_dev  (n_pairs) int64 on the device; start[b] is this call's crop position of pair b
+ *   slots_dev   (n_slots) int32 on the device: the pairs to gather, in output order (any subset, any order)
+ *   out_dev     (n_slots, channels, crop_len) float32: out[s][c][i] = input slots[s], channel c, sample start + i, and 0 where
+ *               start + i lies outside [0, length)
+ * A slot that names no pair, and a pair whose (offset, length) does not lie inside packed_floats, give zeros: nothing outside
+ * the packed buffer is read.  Rows whose source address is 16-byte aligned (offset + c * length + start a multiple of 4 floats
+ * from an aligned base, crop_len % 4 == 0) move 16 bytes per lane, the others one dword per lane. */
+int stito_gather_crops(const float *packed_dev, int64_t packed_floats, const int64_t *offset_dev, const int64_t *length_dev,
+                       const int64_t *start_dev, int n_pairs, const int32_t *slots_dev, int n_slots, int channels,
+                       int64_t crop_len, float *out_dev, void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

@@ -8,8 +8,9 @@ binary plugins.  Of the methods (945-991) `input`, `random`, `rule-based` and `s
 (`--methods`, default `input style-es`); DeepAFx-ST needs a trained checkpoint and its package, which
 do not exist here.  The examples come from `--pairs file` (one "input.wav<TAB>target.wav" per line,
 relative to --root-dir) or `--synthetic N`; the reference's hard-coded file lists are its own
-dataset and are not reproduced.  With `--batched` all examples of equal length are optimised together
-by run_es_batch (BASELINE.json configs[2]) instead of one after the other.
+dataset and are not reproduced.  With `--batched` the examples are optimised together by run_es_batch
+(BASELINE.json configs[2]) instead of one after the other: as one tensor when they all have one shape, as
+lists (per-pair random crops, one GPU batch per evaluate-time length) when their lengths differ.
 
     python st-ito_amd/scripts/eval_pst.py --chain general-pb --synthetic 4 --max-iters 8 --popsize 32
     python st-ito_amd/scripts/eval_pst.py --chain general-pb --synthetic 2 --methods input random rule-based style-es
@@ -118,9 +119,13 @@ def run_pst_benchmark(pairs, plugins, model, out_dir: str, max_iters: int = 32, 
         return r, time.time() - t0
 
     es_out = [None] * len(prepared)
-    if "style-es" in methods and batched and len({(p[1].shape, p[2].shape) for p in prepared}) == 1 and prepared[0][1].shape == prepared[0][2].shape:
+    if "style-es" in methods and batched:
+        # pairs of one shape go as (B, chs, n) tensors, as before; files of different lengths as lists (per-pair crops, one GPU
+        # batch per evaluate-time length)
+        same = len({(p[1].shape, p[2].shape) for p in prepared}) == 1 and prepared[0][1].shape == prepared[0][2].shape
+        xs, ts = [p[1] for p in prepared], [p[2] for p in prepared]
         t0 = time.time()
-        res = run_es_batch(torch.cat([p[1] for p in prepared]), torch.cat([p[2] for p in prepared]), sr, plugins, model,
+        res = run_es_batch(torch.cat(xs) if same else xs, torch.cat(ts) if same else ts, sr, plugins, model,
                            get_param_embeds, max_iters=max_iters, sigma0=sigma0, popsize=popsize, random_crop=random_crop, seed=seed)
         dt = (time.time() - t0) / len(prepared)
         es_out = [(r, dt) for r in res]

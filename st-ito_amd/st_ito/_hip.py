@@ -67,6 +67,9 @@ _lib = None
 SIGNATURES = {
     "stito_last_error": (c_char_p, []),
     "stito_version": (c_int, []),
+    "stito_version_minor": (c_int, []),
+    "stito_gather_crops": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_void_p,
+                                   c_void_p]),
     "stito_fx_num_params": (c_int, [c_int]),
     "stito_chorus_lfo": (c_int, [ctypes.c_double, ctypes.c_double, c_int64, c_void_p, c_void_p]),
     "stito_dasp_compressor": (c_int, [c_void_p, c_int, c_int, c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -17,6 +17,88 @@ import torch
 from . import _hip
 
 CROP_LEN = 262144  # style_transfer.py:505
+CROP_MARGIN = 16384  # style_transfer.py:506-514: a crop start is drawn only when more than this many samples are spare
+
+
+# --------------------------------------------------------------------------------------------
+# length policy of the evaluate step (style_transfer.py:505-518), as pure host functions
+# --------------------------------------------------------------------------------------------
+def crop_start(n: int, random_crop: bool, rng=np.random) -> int:
+    """Crop position of one evaluate call on an input of n samples: rng.randint(16384, n - 262144) when random_crop and more
+    than 16384 samples are spare, else 0 -- and then nothing is drawn from rng."""
+    spare = int(n) - CROP_LEN
+    if random_crop and spare > CROP_MARGIN:
+        return int(rng.randint(CROP_MARGIN, spare))
+    return 0
+
+
+def eval_length(n: int, random_crop: bool) -> int:
+    """Samples per candidate that evaluate renders for an input of n samples: 262144 (zero padded, or cropped), or all n of a
+    longer input without random_crop."""
+    return CROP_LEN if (random_crop or int(n) <= CROP_LEN) else int(n)
+
+
+def plan_ragged_groups(lengths, random_crop: bool) -> List[Tuple[int, List[int]]]:
+    """Pairs of a ragged batch that can share one GPU pass: [(evaluate-time length, [pair indices in ascending order])], groups
+    in order of their first pair.  With random_crop there is one group (everything is 262144 samples)."""
+    groups: Dict[int, List[int]] = {}
+    for b, n in enumerate(lengths):
+        if int(n) <= 0:
+            raise ValueError(f"input {b} is empty")
+        groups.setdefault(eval_length(n, random_crop), []).append(b)
+    return list(groups.items())
+
+
+class RaggedInputs:
+    """The inputs of a ragged batch on the device, uploaded once: one packed float32 buffer with every (chs, n_b) input back to
+    back (each starting on a 16-byte boundary), their offsets and lengths, and per evaluate-time length one persistent
+    (pairs, chs, length) buffer that stito_gather_crops refills -- one launch per call."""
+
+    def __init__(self, inputs: List[torch.Tensor], device: torch.device):
+        _hip.require_gpu()
+        if not inputs:
+            raise ValueError("no inputs")
+        self.device = device
+        self.channels = int(inputs[0].shape[0])
+        self.lengths = [int(x.shape[-1]) for x in inputs]
+        offsets, total = [], 0
+        for x in inputs:
+            if x.dim() != 2 or x.shape[0] != self.channels:
+                raise ValueError("inputs must be (chs, n) with one channel count")
+            offsets.append(total)
+            total += (x.numel() + 3) // 4 * 4
+        host = torch.zeros(total, dtype=torch.float32)
+        for off, x in zip(offsets, inputs):
+            host[off:off + x.numel()] = x.detach().to(torch.float32).reshape(-1)
+        self.packed = host.to(device)
+        self.offset = torch.tensor(offsets, dtype=torch.int64, device=device)
+        self.length = torch.tensor(self.lengths, dtype=torch.int64, device=device)
+        self.start = torch.zeros(len(inputs), dtype=torch.int64, device=device)
+        self._slots = torch.zeros(len(inputs), dtype=torch.int32, device=device)
+        self._out: Dict[int, torch.Tensor] = {}
+        self.n_launches = 0
+
+    def gather(self, pairs: List[int], starts: List[int], crop_len: int) -> torch.Tensor:
+        """(len(pairs), chs, crop_len): samples [start, start + crop_len) of the listed inputs, zeros past their ends (a pair has ONE
+        start per call, so it is listed at most once).  The result is a view of a buffer that the next gather of the same crop_len overwrites (same stream: ordered)."""
+        n_pairs, k = len(self.lengths), len(pairs)
+        if k == 0 or len(set(pairs)) != k or len(starts) != k or any(not 0 <= b < n_pairs for b in pairs):
+            raise ValueError(f"gather: pairs {list(pairs)} / starts {list(starts)} do not name inputs 0 .. {n_pairs - 1}")
+        if any(s < 0 or s >= self.lengths[b] for b, s in zip(pairs, starts)):
+            raise ValueError(f"gather: a crop start lies outside its input ({list(starts)})")
+        buf = self._out.get(crop_len)
+        if buf is None:
+            buf = self._out[crop_len] = torch.empty((n_pairs, self.channels, crop_len), dtype=torch.float32, device=self.device)
+        st = np.zeros(n_pairs, dtype=np.int64)
+        st[list(pairs)] = starts
+        self.start.copy_(torch.from_numpy(st))
+        self._slots[:k].copy_(torch.tensor(list(pairs), dtype=torch.int32))
+        out = buf[:k]
+        _hip.check(_hip.lib().stito_gather_crops(_hip.ptr(self.packed), self.packed.numel(), _hip.ptr(self.offset), _hip.ptr(self.length),
+                                                 _hip.ptr(self.start), n_pairs, _hip.ptr(self._slots), k, self.channels, crop_len,
+                                                 _hip.ptr(out), _hip.stream_ptr()))
+        self.n_launches += 1
+        return out
 
 
 # --------------------------------------------------------------------------------------------
@@ -191,7 +273,9 @@ class PopulationEvaluator:
 
     Multi-pair batches (BASELINE.json configs[2]): x may hold B inputs (B, C, L) with B target
     embeddings (B, E); evaluate then takes the B populations stacked pair-major, (B * P, D), and
-    scores the candidates of pair b against target b."""
+    scores the candidates of pair b against target b.  evaluate(W, pairs=[...], x=buffer) scores the populations of a SUBSET
+    of the pairs, in the order listed, on a ready-made input buffer (len(pairs), C, L) -- the ragged batch, which gathers,
+    renders and embeds its active pairs only.  `rendered_candidates` counts what went through the render."""
 
     def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], model, target_embeds: dict,
                  device: Optional[torch.device] = None, max_candidates_per_pass: Optional[int] = None,
@@ -255,6 +339,7 @@ class PopulationEvaluator:
         self._graph_evictions = 0
         self._graphs = {}      # (P, input pointer, input shape) -> (graph, W buffer, loss, mid, side, n_calls, buffers kept alive)
         self._x_padded = None
+        self.rendered_candidates = 0
 
     def _input(self, random_crop: bool, rng, parallel: bool = False) -> torch.Tensor:
         """Length policy of style_transfer.py:505-518 (one crop position for all inputs of a batch).  The reference's
@@ -274,13 +359,21 @@ class PopulationEvaluator:
             self._x_padded = torch.nn.functional.pad(x, (0, CROP_LEN - n)).contiguous()
         return self._x_padded
 
-    def _fused_pass(self, Wc, x, p0, p1, per, n_calls, dropout, want_audio):
+    def _spans(self, p0, p1, per, pairs):
+        """-> (inputs of x that candidates p0 .. p1 - 1 read, [(target index, first candidate, end) within the pass])"""
+        B = self.n_inputs if pairs is None else len(pairs)
+        tgt = (lambda b: b) if pairs is None else (lambda b: pairs[b])
+        if B == 1:
+            return (0, 1), [(tgt(0), 0, p1 - p0)]
+        b0, b1 = p0 // per, (p1 + per - 1) // per
+        return (b0, b1), [(tgt(b), (b - b0) * per, (b - b0 + 1) * per) for b in range(b0, b1)]
+
+    def _fused_pass(self, Wc, x, p0, p1, per, n_calls, dropout, want_audio, pairs=None):
         """One pass of the fused AFx-Rep path over candidates p0 .. p1 - 1 on the current stream:
         render -> log-mel + Cnn14 -> loss.  -> (loss, mid, side, audio or None, peaks, n_calls)"""
         L = _hip.lib()
-        B = self.n_inputs
-        b0, b1 = p0 // per, (p1 + per - 1) // per
-        xin = x[0] if B == 1 else x[b0:b1]
+        (b0, b1), spans = self._spans(p0, p1, per, pairs)
+        xin = x[0] if x.shape[0] == 1 else x[b0:b1]
         audio, peaks = render_population(self.plugins, xin, Wc, self.sample_rate, chain=self.chain)
         mid, side = self.model.embed_raw(audio, peaks, norm_passes=2)
         loss = torch.empty(mid.shape[0], dtype=torch.float32, device=self.device)
@@ -291,7 +384,6 @@ class PopulationEvaluator:
         if dropout > 0.0:
             md = torch.nn.functional.dropout(mid, p=dropout, training=True).contiguous()
             sd = torch.nn.functional.dropout(side, p=dropout, training=True).contiguous()
-        spans = [(0, 0, p1 - p0)] if B == 1 else [(b, (b - b0) * per, (b - b0 + 1) * per) for b in range(b0, b1)]
         for b, q0, q1 in spans:  # candidates of pair b against target b
             _hip.check(L.stito_embed_loss(_hip.ptr(md[q0:q1]), _hip.ptr(sd[q0:q1]), q1 - q0, mid.shape[1],
                                           _hip.ptr(self.tmid[b]), _hip.ptr(self.tside[b]), _hip.ptr(loss[q0:q1]),
@@ -363,20 +455,38 @@ class PopulationEvaluator:
         g, Wbuf, loss, mid, side, n_calls, _ = ent
         Wbuf.copy_(torch.from_numpy(Wn))
         g.replay()
+        self.rendered_candidates += P
         self._n_flag_rows = min(n_calls, 255)
         return loss.clone(), {"mid": mid.clone(), "side": side.clone()}, None
 
     def evaluate(self, W, random_crop: bool = False, rng=np.random, want_audio: bool = False, dropout: float = 0.0,
-                 parallel: bool = False):
+                 parallel: bool = False, pairs=None, x: Optional[torch.Tensor] = None):
         """Fitness of every row of W -> (loss (P,), embeddings dict, normalised audio or None).  The population goes through in
         passes of at most `max_candidates_per_pass` candidates (whole pairs for a multi-pair batch), one after the other on the
-        current stream; a candidate's result does not depend on how the population is cut."""
+        current stream; a candidate's result does not depend on how the population is cut.
+
+        pairs: indices of the inputs / targets that the pair-major blocks of W belong to (default: all of them, in order).
+        x: a ready-made evaluate-time input buffer (len(pairs), C, L) float32 on the device, used as it is -- no padding, no
+        crop, nothing drawn from rng; without it the listed pairs are taken from the evaluator's own input by the length policy
+        (one crop position for all).  Calls with `pairs` or `x` launch eagerly (no graph replay)."""
         Wn = np.asarray(W, dtype=np.float64)
         if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
             raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
-        x = self._input(random_crop, rng, parallel)
+        subset = pairs is not None or x is not None
+        if pairs is not None:
+            pairs = [int(b) for b in pairs]
+            if not pairs or any(not 0 <= b < self.n_inputs for b in pairs):
+                raise ValueError(f"pairs {pairs} do not name inputs 0 .. {self.n_inputs - 1}")
+        if x is None:
+            x = self._input(random_crop, rng, parallel)
+            if pairs is not None:
+                x = x[pairs].contiguous()
+        else:
+            n_x = self.n_inputs if pairs is None else len(pairs)
+            if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous() and x.shape[0] == n_x):
+                raise ValueError(f"x must be a contiguous ({n_x}, chs, n) float32 tensor on the GPU")
         P = Wn.shape[0]
-        B = self.n_inputs
+        B = x.shape[0]
         if P == 0 or P % B:
             raise ValueError(f"{P} candidates cannot be split over {B} inputs")
         per = P // B  # candidates per input
@@ -385,7 +495,7 @@ class PopulationEvaluator:
             step = max(per, step // per * per)
         bounds = [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
         cropped = random_crop and not parallel and self.x_full.shape[-1] > CROP_LEN   # a new input buffer per call
-        if (self._graph_on and self.fused and len(bounds) == 1 and dropout == 0.0 and not want_audio and not cropped and
+        if (self._graph_on and self.fused and len(bounds) == 1 and dropout == 0.0 and not want_audio and not cropped and not subset and
                 not torch.cuda.is_current_stream_capturing()):
             out = self._evaluate_graph(Wn, x, per)
             if out is not None:
@@ -395,14 +505,14 @@ class PopulationEvaluator:
         n_calls = 0
         for p0, p1 in bounds:
             Wc = Wt[p0:p1].contiguous()
+            self.rendered_candidates += p1 - p0
             if self.fused:
-                loss, mid, side, audio, _, n_calls = self._fused_pass(Wc, x, p0, p1, per, n_calls, dropout, want_audio)
+                loss, mid, side, audio, _, n_calls = self._fused_pass(Wc, x, p0, p1, per, n_calls, dropout, want_audio, pairs)
                 mids.append(mid); sides.append(side)
             else:
-                b0, b1 = p0 // per, (p1 + per - 1) // per
+                (b0, b1), spans = self._spans(p0, p1, per, pairs)
                 xin = x[0] if B == 1 else x[b0:b1]
                 audio, peaks = render_population(self.plugins, xin, Wc, self.sample_rate, chain=self.chain)
-                spans = [(0, 0, p1 - p0)] if B == 1 else [(b, (b - b0) * per, (b - b0 + 1) * per) for b in range(b0, b1)]
                 loss, emb = self._generic_loss(normalize_audio_(audio, peaks), spans, dropout)
                 generic_embeds.append(emb)
             losses.append(loss)

@@ -575,15 +575,31 @@ def run_es_batch(
 
     The reference optimises its examples one after the other (scripts/eval/eval_pst.py:691-765)
     and its evaluate closure assumes one input (style_transfer.py:520).  Here every pair keeps its
-    own CMA-ES state (seed + pair index) and each iteration evaluates the B populations, stacked
+    own CMA-ES state (seed + pair index) and each iteration evaluates the populations, stacked
     pair-major as (B * popsize, D), in one pass over the GPU; pair b's candidates read input b and
-    are scored against target b.  A pair's trajectory is bitwise the one `run_es(find_w0=False,
-    seed=seed + b)` produces for it alone.  Pairs that stop early (same rule as run_es, lines
-    655-670) keep being evaluated with their last population but are no longer told.
+    are scored against target b.  Two forms of the call:
 
-    input_audios / target_audios: (B, chs, seq_len), all pairs the same length and channel count.
+    Tensors -- input_audios / target_audios (B, chs, seq_len), all pairs the same length and channel count.  One crop
+    position per iteration, drawn from RandomState(seed), serves all pairs, and pairs that stop early (same rule as run_es,
+    lines 655-670) keep being evaluated with their last population but are no longer told.  A pair's trajectory is bitwise
+    the one `run_es(find_w0=False, seed=seed + b)` produces for it alone AS LONG AS NO CROP IS DRAWN (random_crop=False, or
+    seq_len <= 262144 + 16384).
+
+    Lists -- two lists of B tensors (1, chs, n_b) or (chs, n_b): the inputs share a channel count and may differ in length,
+    the targets may differ in length from their inputs and from each other (the PST benchmark's files).  Pair b draws its
+    own crop positions from RandomState(seed + b) (engine.crop_start: one draw per iteration while the pair is active, none
+    when the rule needs none); pairs are grouped by evaluate-time length (engine.plan_ragged_groups: everything is 262144
+    samples under random_crop or when the file is shorter) and every group is one GPU batch per iteration, its inputs cut
+    out of one packed device buffer by stito_gather_crops; pairs that have stopped are no longer gathered, rendered or
+    embedded; the targets are embedded once, those of equal length in one call.  The bitwise promise above holds for this
+    form ALWAYS, `random_crop=True` on long inputs included.  The launches are eager (no graph replay).
+
+    Each pair is peak-normalised on its own, on clones: the caller's tensors are not modified.
     Under torch.distributed the PAIRS are sharded over the ranks (no collective until
     the final gather); every rank returns the full list of B result dicts."""
+    if isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple)):
+        return _run_es_batch_ragged(input_audios, target_audios, sample_rate, plugins, model, embed_func, max_iters, sigma0,
+                                    popsize, random_crop, seed, early_stop)
     if input_audios.dim() != 3 or target_audios.dim() != 3 or input_audios.shape[0] != target_audios.shape[0]:
         raise ValueError("input_audios and target_audios must be (B, chs, seq_len) with the same B")
     dist, rank, world = _dist_info()
@@ -635,6 +651,125 @@ def run_es_batch(
         for b, st in enumerate(states):
             wopt, fopt = st["es"].result[0], st["es"].result[1]
             out = torch.from_numpy(process_audio(xs[b].cpu().numpy(), wopt, sample_rate, plugins))
+            results[lo + b] = {"output_audio": out, "params": parameters_to_dict(wopt, plugins), "fopt": fopt, "wopt": wopt,
+                               "fval_history": st["fval_history"], "wopt_history": st["wopt_history"],
+                               "num_evals": st["n_evals"]}
+    if world > 1:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, [(i, r) for i, r in enumerate(results) if r is not None])
+        for part in gathered:
+            for i, r in part:
+                results[i] = r
+    return results
+
+
+def _check_ragged_pairs(input_audios, target_audios):
+    """Validation of the list form of run_es_batch (host only) -> ([(chs, n_b)], [(chs_t, m_b)]) views of the caller's tensors."""
+    if not isinstance(input_audios, (list, tuple)) or not isinstance(target_audios, (list, tuple)):
+        raise ValueError("input_audios and target_audios must both be lists (or both (B, chs, seq_len) tensors)")
+    if len(input_audios) == 0 or len(target_audios) == 0:
+        raise ValueError("input_audios and target_audios must not be empty")
+    if len(input_audios) != len(target_audios):
+        raise ValueError(f"{len(input_audios)} inputs but {len(target_audios)} targets")
+
+    def as_2d(a, what, b):
+        if not isinstance(a, torch.Tensor):
+            raise ValueError(f"{what} {b}: expected a tensor, got {type(a).__name__}")
+        if a.dim() == 3 and a.shape[0] == 1:
+            a = a[0]
+        if a.dim() != 2 or a.shape[0] not in (1, 2) or a.shape[1] == 0:
+            raise ValueError(f"{what} {b}: expected (1, chs, n) or (chs, n) with 1 or 2 channels, got {tuple(a.shape)}")
+        return a
+
+    xs = [as_2d(a, "input", b) for b, a in enumerate(input_audios)]
+    ts = [as_2d(a, "target", b) for b, a in enumerate(target_audios)]
+    if len({x.shape[0] for x in xs}) != 1:
+        raise ValueError(f"inputs have mixed channel counts {[x.shape[0] for x in xs]}")
+    return xs, ts
+
+
+def _run_es_batch_ragged(input_audios, target_audios, sample_rate, plugins, model, embed_func, max_iters, sigma0, popsize,
+                         random_crop, seed, early_stop):
+    """The list form of run_es_batch (see there)."""
+    xs_all, ts_all = _check_ragged_pairs(input_audios, target_audios)
+    dist, rank, world = _dist_info()
+    B_all = len(xs_all)
+    if world > 1 and seed is None:  # the ranks own different pairs, but a pair's seed must not depend on the sharding
+        box = [int(np.random.SeedSequence().generate_state(1)[0] & 0x7FFFFFFF) if rank == 0 else None]
+        dist.broadcast_object_list(box, src=0)
+        seed = box[0]
+    lo, hi = shard_bounds(B_all, rank, world)
+    results = [None] * B_all
+    if hi > lo:
+        B = hi - lo
+        total_num_params = sum([plugin["num_params"] for plugin in plugins.values()])
+
+        def normalised(a):  # run_es 452-453, on a float32 CPU clone
+            a = a.detach().to("cpu", torch.float32).clone()
+            a /= torch.max(torch.abs(a)).clamp(min=1e-8)
+            return a
+
+        xs = [normalised(a) for a in xs_all[lo:hi]]
+        ts = [normalised(a) for a in ts_all[lo:hi]]
+        # target embeddings, once: targets of equal shape in one embed_func call
+        by_shape, rows = {}, [None] * B
+        for b, t in enumerate(ts):
+            by_shape.setdefault(tuple(t.shape), []).append(b)
+        for members in by_shape.values():
+            emb = embed_func(torch.stack([ts[b] for b in members]), model, sample_rate)
+            for k, b in enumerate(members):
+                rows[b] = {name: v.detach().reshape(len(members), -1)[k] for name, v in emb.items()}
+        target_embed = {name: torch.stack([rows[b][name] for b in range(B)]) for name in rows[0]}
+        device = torch.device("cuda", torch.cuda.current_device())
+        ragged = engine.RaggedInputs(xs, device)
+        # the evaluator never reads its own input on this path (every call brings its gathered buffer): a one-sample stand-in
+        evaluator = engine.PopulationEvaluator(torch.zeros((B, xs[0].shape[0], 1)), sample_rate, plugins, model, target_embed,
+                                               embed_func=embed_func, use_graph=False)
+        if evaluator.ndims != total_num_params:
+            raise ValueError(f"plugins declare {total_num_params} params, chain consumes {evaluator.ndims}")
+        states = []
+        for b in range(B):
+            opts = {"bounds": [0, 1], "popsize": popsize}
+            if seed is not None:
+                opts["seed"] = seed + lo + b
+            states.append(dict(es=cma.CMAEvolutionStrategy(np.ones(total_num_params) * 0.5, sigma0, opts), fval_history=[],
+                               wopt_history=[], stale=0, active=True, W=None, n_evals=0,
+                               rng=np.random.RandomState(seed + lo + b) if seed is not None else np.random))
+        groups = engine.plan_ragged_groups(ragged.lengths, random_crop)
+        for iteration in range(max_iters):
+            if not any(st["active"] for st in states):
+                break
+            for st in states:
+                if st["active"]:
+                    st["W"] = st["es"].ask()
+            pending = []
+            for eval_len, members in groups:  # one gather + one evaluate per group, queued before any fitness is fetched
+                act = [b for b in members if states[b]["active"]]
+                if not act:
+                    continue
+                starts = [engine.crop_start(ragged.lengths[b], random_crop, states[b]["rng"]) for b in act]
+                x = ragged.gather(act, starts, eval_len)
+                loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(states[b]["W"]) for b in act], 0), pairs=act, x=x)
+                pending.append((act, loss))
+            for st in states:  # the next generation's normal deviates, drawn while the GPU works (as run_es does)
+                if st["active"]:
+                    st["es"].prefetch()
+            for act, loss in pending:
+                fv = loss.tolist()
+                for k, b in enumerate(act):
+                    st = states[b]
+                    fvals = fv[k * popsize:(k + 1) * popsize]
+                    st["n_evals"] += popsize
+                    st["wopt_history"].append(st["es"].result[0])
+                    st["fval_history"].append(st["es"].result[1])
+                    st["es"].tell(st["W"], fvals)
+                    stale = iteration > 0 and min(fvals) - min(st["fval_history"]) > -0.01
+                    st["stale"] = st["stale"] + 1 if stale else 0
+                    if early_stop and st["stale"] > 10:
+                        st["active"] = False
+        for b, st in enumerate(states):
+            wopt, fopt = st["es"].result[0], st["es"].result[1]
+            out = torch.from_numpy(process_audio(xs[b].numpy(), wopt, sample_rate, plugins))
             results[lo + b] = {"output_audio": out, "params": parameters_to_dict(wopt, plugins), "fopt": fopt, "wopt": wopt,
                                "fval_history": st["fval_history"], "wopt_history": st["wopt_history"],
                                "num_evals": st["n_evals"]}

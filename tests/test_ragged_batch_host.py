@@ -1,0 +1,104 @@
+"""CPU tests of the ragged multi-pair batch's host side: the crop rule, the group planner and the list-form validation of
+run_es_batch (all of which run before anything touches the GPU)."""
+import numpy as np
+import pytest
+import torch
+
+CROP, MARGIN = 262144, 16384
+LENGTHS = [1000, CROP, CROP + MARGIN, CROP + MARGIN + 1, 600000]
+
+
+class _CountingRng:
+    """A RandomState that counts its randint calls."""
+
+    def __init__(self, seed):
+        self.rs = np.random.RandomState(seed)
+        self.calls = []
+
+    def randint(self, lo, hi):
+        self.calls.append((lo, hi))
+        return self.rs.randint(lo, hi)
+
+
+@pytest.mark.parametrize("n", LENGTHS)
+@pytest.mark.parametrize("random_crop", [False, True])
+def test_crop_start_is_the_literal_rule(n, random_crop):
+    from st_ito.engine import CROP_LEN, crop_start
+    assert CROP_LEN == CROP
+    rng, ref = _CountingRng(7), np.random.RandomState(7)
+    got = [crop_start(n, random_crop, rng) for _ in range(5)]
+    if random_crop and n - CROP > MARGIN:
+        want = [int(ref.randint(MARGIN, n - CROP)) for _ in range(5)]
+        assert rng.calls == [(MARGIN, n - CROP)] * 5
+        assert all(MARGIN <= s < n - CROP for s in got)
+    else:
+        want = [0] * 5
+        assert rng.calls == []       # a pair that needs no draw consumes none
+    assert got == want and all(type(s) is int for s in got)
+
+
+def test_crop_start_draw_sequence_interleaves_with_pairs_that_draw_nothing():
+    """Two pairs on ONE seeded generator: the short one must leave the long one's sequence untouched."""
+    from st_ito.engine import crop_start
+    rng, ref = np.random.RandomState(11), np.random.RandomState(11)
+    got = []
+    for _ in range(4):
+        assert crop_start(270000, True, rng) == 0      # spare 7856 <= 16384: cropped at 0, no draw
+        assert crop_start(1000, True, rng) == 0
+        got.append(crop_start(400000, True, rng))
+    assert got == [int(ref.randint(MARGIN, 400000 - CROP)) for _ in range(4)]
+    # the smallest input that draws has exactly one possible start
+    assert crop_start(CROP + MARGIN + 1, True, np.random.RandomState(0)) == MARGIN
+
+
+def test_eval_length_and_group_planner():
+    from st_ito.engine import eval_length, plan_ragged_groups
+    for n in LENGTHS:
+        assert eval_length(n, True) == CROP
+        assert eval_length(n, False) == (CROP if n <= CROP else n)
+    assert plan_ragged_groups([200000, 270000, 400000, 1000], True) == [(CROP, [0, 1, 2, 3])]   # random_crop: one group
+    assert plan_ragged_groups([300000, 300000, 350000], False) == [(300000, [0, 1]), (350000, [2])]
+    # short files (and files of exactly 262144 samples) join the 262144 group; groups come in order of their first pair
+    assert plan_ragged_groups([300000, 1000, CROP, 300000, 200000], False) == [(300000, [0, 3]), (CROP, [1, 2, 4])]
+    assert plan_ragged_groups([5], False) == [(CROP, [0])]
+    with pytest.raises(ValueError):
+        plan_ragged_groups([1000, 0], True)
+
+
+def test_list_form_validation_raises_before_any_gpu_call(monkeypatch):
+    from st_ito import _hip, engine
+    from st_ito.style_transfer import run_es_batch
+
+    def no_gpu(*a, **k):
+        raise AssertionError("validation must not reach the GPU")
+
+    monkeypatch.setattr(_hip, "lib", no_gpu)
+    monkeypatch.setattr(_hip, "require_gpu", no_gpu)
+    monkeypatch.setattr(engine, "PopulationEvaluator", no_gpu)
+    embed = no_gpu
+    st = lambda n: torch.zeros(1, 2, n)                     # noqa: E731
+    call = lambda xs, ts: run_es_batch(xs, ts, 48000, {}, None, embed, max_iters=1, popsize=4)   # noqa: E731
+    with pytest.raises(ValueError, match="2 inputs but 1 targets"):
+        call([st(100), st(200)], [st(100)])
+    with pytest.raises(ValueError, match="empty"):
+        call([], [])
+    with pytest.raises(ValueError, match="mixed channel counts"):
+        call([st(100), torch.zeros(1, 1, 200)], [st(100), st(50)])
+    with pytest.raises(ValueError, match="both be lists"):
+        call([st(100)], torch.zeros(1, 2, 100))
+    with pytest.raises(ValueError, match="input 1"):
+        call([st(100), torch.zeros(2, 2, 100)], [st(100), st(100)])     # a batch of two is not one pair
+    with pytest.raises(ValueError, match="target 0"):
+        call([st(100)], [torch.zeros(100)])
+    with pytest.raises(ValueError, match="input 0"):
+        call([torch.zeros(2, 0)], [st(100)])
+
+
+def test_binding_declares_the_gather_symbol():
+    from st_ito import _hip
+    assert "stito_gather_crops" in _hip.SIGNATURES and len(_hip.SIGNATURES["stito_gather_crops"][1]) == 12
+    lib = _hip.lib()
+    assert lib.stito_version_minor() >= 1
+    # argument checks happen on the host, before any launch
+    assert lib.stito_gather_crops(None, 0, None, None, None, 0, None, 0, 2, 4, None, None) == _hip.E_INVALID
+    assert b"stito_gather_crops" in lib.stito_last_error()
