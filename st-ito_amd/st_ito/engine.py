@@ -20,6 +20,12 @@ CROP_LEN = 262144  # style_transfer.py:505
 CROP_MARGIN = 16384  # style_transfer.py:506-514: a crop start is drawn only when more than this many samples are spare
 
 
+def _current_device() -> torch.device:
+    """The GPU that this process works on; without one there is nothing to fall back to."""
+    _hip.require_gpu()
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 # --------------------------------------------------------------------------------------------
 # length policy of the evaluate step (style_transfer.py:505-518), as pure host functions
 # --------------------------------------------------------------------------------------------
@@ -152,8 +158,7 @@ def compile_chain(plugins: Dict[str, dict], normalize_stages: bool = False) -> T
         d.fixed_mask = mask
         d.flags = _hip.FX_FLAG_NORMALIZE_AFTER if normalize_stages else 0  # style_transfer.py:106-107
         if kind == _hip.FX_NOISE_REVERB:  # the band-filtered noise bank is an input of the stage
-            _hip.require_gpu()
-            bank = inst.noise_bank_device(torch.device("cuda", torch.cuda.current_device()))
+            bank = inst.noise_bank_device(_current_device())
             descs._keep.append(bank)
             d.aux_dev, d.aux_len = bank.data_ptr(), bank.shape[-1]
         off += len(names)
@@ -233,7 +238,7 @@ def normalize_audio_(audio: torch.Tensor, peaks: torch.Tensor) -> torch.Tensor:
 
 def render_single(instance, x: np.ndarray, sample_rate: float) -> np.ndarray:
     """Basic*.process(x, sample_rate): one effect, current parameter values, (chs, n) -> (chs', n)."""
-    _hip.require_gpu()
+    dev = _current_device()
     x = np.ascontiguousarray(x, dtype=np.float32)
     if x.ndim != 2:
         raise ValueError("process expects a (chs, n) array")
@@ -244,7 +249,6 @@ def render_single(instance, x: np.ndarray, sample_rate: float) -> np.ndarray:
                       "fixed_parameters": {}, "parameter_names": list(instance.parameters.keys()),
                       "num_params": len(instance.parameters)}}
     w = np.array([[p.raw_value for p in instance.parameters.values()]], dtype=np.float64)
-    dev = torch.device("cuda", torch.cuda.current_device())
     audio, _ = render_population(plugins, torch.from_numpy(x).to(dev), torch.from_numpy(w).to(dev), sample_rate)
     return audio[0].cpu().numpy()
 
@@ -252,8 +256,7 @@ def render_single(instance, x: np.ndarray, sample_rate: float) -> np.ndarray:
 def process_audio_gpu(x: np.ndarray, w: np.ndarray, sr: int, plugins: Dict[str, dict],
                       normalize_stages: bool = False) -> np.ndarray:
     """process_audio for one parameter vector (style_transfer.py:45-115)."""
-    _hip.require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _current_device()
     xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
     wt = torch.as_tensor(np.asarray(w, dtype=np.float64)[None, :]).to(dev)
     audio, peaks = render_population(plugins, xt, wt, sr, chain=compile_chain(plugins, normalize_stages))
@@ -291,7 +294,7 @@ class PopulationEvaluator:
         _hip.require_gpu()
         from . import utils as _utils
 
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.device = device or _current_device()
         self.sample_rate = sample_rate
         self.plugins = plugins
         self.model = model
@@ -342,21 +345,20 @@ class PopulationEvaluator:
         self.rendered_candidates = 0
 
     def _input(self, random_crop: bool, rng, parallel: bool = False) -> torch.Tensor:
-        """Length policy of style_transfer.py:505-518 (one crop position for all inputs of a batch).  The reference's
-        parallel=True branch (499-502) hands x to the pool as it is: no padding to 262144, no crop."""
+        """Length policy of style_transfer.py:505-518 -- crop_start and eval_length -- with one crop position for all inputs of a
+        batch.  The reference's parallel=True branch (499-502) hands x to the pool as it is: no padding to 262144, no crop, and
+        nothing drawn from rng."""
         x = self.x_full
-        n = x.shape[-1]
         if parallel:
             return x
-        if n > CROP_LEN:
-            if random_crop:  # 506-514: start 0 unless more than 16384 samples are spare (the crop still happens)
-                start = int(rng.randint(16384, n - CROP_LEN)) if (n - CROP_LEN) > 16384 else 0
-                return x[..., start:start + CROP_LEN].contiguous()
+        n = x.shape[-1]
+        start, length = crop_start(n, random_crop, rng), eval_length(n, random_crop)
+        if length == n:  # a long input without random_crop, or exactly 262144 samples: as it is, no copy
             return x
-        if n == CROP_LEN:
-            return x
+        if length < n:  # cropped, at 0 when no start was drawn
+            return x[..., start:start + length].contiguous()
         if self._x_padded is None:  # padded once: the same buffer for every call (a captured graph reads it)
-            self._x_padded = torch.nn.functional.pad(x, (0, CROP_LEN - n)).contiguous()
+            self._x_padded = torch.nn.functional.pad(x, (0, length - n)).contiguous()
         return self._x_padded
 
     def _spans(self, p0, p1, per, pairs):
@@ -494,7 +496,8 @@ class PopulationEvaluator:
         if B > 1:  # passes hold whole pairs
             step = max(per, step // per * per)
         bounds = [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
-        cropped = random_crop and not parallel and self.x_full.shape[-1] > CROP_LEN   # a new input buffer per call
+        n_full = self.x_full.shape[-1]
+        cropped = not parallel and eval_length(n_full, random_crop) < n_full   # a new input buffer per call
         if (self._graph_on and self.fused and len(bounds) == 1 and dropout == 0.0 and not want_audio and not cropped and not subset and
                 not torch.cuda.is_current_stream_capturing()):
             out = self._evaluate_graph(Wn, x, per)

@@ -8,7 +8,12 @@ one random parameter vector through the GPU render) and `run_rule_based` (163-27
 then a compressor threshold hill-climb, every item of the batch at once on the GPU -- csrc/matcheq.hip, st_ito.matcheq),
 with the reference's `get_average_spectrum` and `smooth_spectrum`.  `run_deepafx_st` is not: it needs a trained
 DeepAFx-ST checkpoint and its package.  `run_es_batch` is an extension (BASELINE.json configs[2]): several (input,
-target) pairs optimised together, every iteration evaluating all their populations in one GPU batch.
+target) pairs optimised together, every iteration evaluating their populations in one GPU batch (or one per input length).
+
+The three ES drivers share one statement of each rule: `_EsRun` is one CMA-ES trajectory with the reference's bookkeeping
+(617-670: pre-tell histories, evaluation count, the stale counter of the early stop) and the result dict; `_agree_on_seed`,
+`_peak_normalize_` and `_chain_dims` are the steps every driver takes before its first iteration.  `run_es` steps one `_EsRun`,
+`run_es_batch` a list of them, `run_staged_es` builds one per stage and keeps run_optim.py's own post-tell histories.
 """
 from __future__ import annotations
 
@@ -149,7 +154,7 @@ def smooth_spectrum(H):
 
     as_numpy = not isinstance(H, torch.Tensor)
     h = torch.as_tensor(np.asarray(H) if as_numpy else H)
-    dev = h.device if h.is_cuda else _gpu_device()
+    dev = h.device if h.is_cuda else engine._current_device()
     rows = h.detach().to(dev, torch.float32).reshape(-1, h.shape[-1]).contiguous()
     out = matcheq.savgol(rows).reshape(h.shape)
     return out.cpu().numpy() if as_numpy else out.to(h.device)
@@ -163,16 +168,9 @@ def get_average_spectrum(x: torch.Tensor, n_fft: int = 16384):
 
     print(x.shape)
     _check_rule_based_shape(x[None], n_fft, None, "x")
-    dev = x.device if x.is_cuda else _gpu_device()
+    dev = x.device if x.is_cuda else engine._current_device()
     xs = x.detach().to(dev, torch.float32)[None].contiguous()
     return matcheq.mean_spectrum(xs, n_fft)[0].to(x.device)
-
-
-def _gpu_device():
-    from . import _hip
-
-    _hip.require_gpu()
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _check_rule_based_shape(x: torch.Tensor, n_fft: int, sample_rate, name: str):
@@ -211,7 +209,7 @@ def run_rule_based(input_audio: torch.Tensor, target_audio: torch.Tensor, sample
         raise ValueError(f"input_audio has {bs} items, target_audio {target_audio.shape[0]}")
     if not 16 <= n_taps <= 4096:
         raise NotImplementedError(f"n_taps {n_taps}: only 16 .. 4096 are built")
-    dev = _gpu_device()
+    dev = engine._current_device()
 
     def normalised(a):  # peak normalise to -12 dBFS on the GPU, then write back into the caller's tensor
         g = matcheq.peak_normalize_(a.detach().to(dev, torch.float32).contiguous())
@@ -285,6 +283,90 @@ def sharded_evaluate(W, eval_local, while_waiting=None):
     return gather_fitness(loss, P).tolist(), embeds, audios
 
 
+def _agree_on_seed(seed):
+    """`seed`, or for an unseeded run under torch.distributed a seed that rank 0 draws and broadcasts: the ranks step replicas of
+    one CMA-ES state (or own different pairs whose seeds must not depend on the sharding), so every seeded draw -- CMA-ES,
+    find_w0, crop positions -- has to agree.  A single-rank run enters no collective and stays unseeded."""
+    dist, rank, world = _dist_info()
+    if world > 1 and seed is None:
+        box = [int(np.random.SeedSequence().generate_state(1)[0] & 0x7FFFFFFF) if rank == 0 else None]
+        dist.broadcast_object_list(box, src=0)
+        seed = box[0]
+    return seed
+
+
+def _peak_normalize_(audio: torch.Tensor) -> torch.Tensor:
+    """In place: audio /= max|audio| (reference 452-453)."""
+    audio /= torch.max(torch.abs(audio)).clamp(min=1e-8)
+    return audio
+
+
+def _chain_dims(evaluator, plugins) -> int:
+    """Number of parameter slots of the plugins, which must be what the compiled chain consumes."""
+    total_num_params = sum([plugin["num_params"] for plugin in plugins.values()])
+    if evaluator.ndims != total_num_params:
+        raise ValueError(f"plugins declare {total_num_params} params, chain consumes {evaluator.ndims}")
+    return total_num_params
+
+
+def _es_result(output_audio, wopt, fopt, fval_history, wopt_history, num_evals, plugins, **extra):
+    """The dict every ES driver returns; a driver's own entries (run_staged_es: stage_wopts) go in front of num_evals."""
+    return {
+        "output_audio": output_audio,
+        "params": parameters_to_dict(wopt, plugins),
+        "fopt": fopt,
+        "wopt": wopt,
+        "fval_history": fval_history,
+        "wopt_history": wopt_history,
+        **extra,
+        "num_evals": num_evals,
+    }
+
+
+class _EsRun:
+    """One CMA-ES trajectory and its bookkeeping (reference 614-673): the strategy, the population of the last ask(), the
+    histories, the evaluation count and the early-stop counter.  Every driver steps its trajectories through this class, which
+    is what makes "pair b of a batch is bitwise the run_es of pair b alone" a matter of construction."""
+
+    @staticmethod
+    def strategy(w0, sigma0, popsize, seed):
+        """The CMA-ES of the reference (614, 624): bounds [0, 1], seeded when a seed is given."""
+        opts = {"bounds": [0, 1], "popsize": popsize}
+        if seed is not None:
+            opts["seed"] = seed
+        return cma.CMAEvolutionStrategy(w0, sigma0, opts)
+
+    def __init__(self, w0, sigma0, popsize, seed):
+        self.es = self.strategy(w0, sigma0, popsize, seed)
+        self.W = None
+        self.fval_history = []
+        self.wopt_history = []
+        self.n_evals = 0
+        self.stale = 0          # consecutive iterations without improvement
+        self.active = True      # a batch clears it when the pair stops early
+
+    def ask(self):
+        self.W = self.es.ask()
+        return self.W
+
+    def tell(self, fvals, iteration) -> bool:
+        """Record the best so far -- the PRE-tell result like the reference, so entry 0 is (None, inf) -- then tell.  -> whether
+        the iteration was stale (reference 655-670): its best candidate did not beat the best value on record by more than 0.01;
+        the first iteration never counts."""
+        self.n_evals += len(self.W)
+        self.wopt_history.append(self.es.result[0])
+        self.fval_history.append(self.es.result[1])
+        self.es.tell(self.W, fvals)
+        stale = iteration > 0 and min(fvals) - min(self.fval_history) > -0.01
+        self.stale = self.stale + 1 if stale else 0
+        return stale
+
+    def result(self, output_audio, plugins):
+        """The result dict, given the render of the current solution es.result[0]."""
+        wopt, fopt = self.es.result[0], self.es.result[1]
+        return _es_result(output_audio, wopt, fopt, self.fval_history, self.wopt_history, self.n_evals, plugins)
+
+
 def run_es(
     input_audio: torch.Tensor,
     target_audio: torch.Tensor,
@@ -322,20 +404,14 @@ def run_es(
         raise ValueError(f"Unknown distance: {distance}")
     if content_model is not None and content_embed_func is None:
         raise ValueError("content_model needs a content_embed_func")
-    total_num_params = sum([plugin["num_params"] for plugin in plugins.values()])
     bs, chs, seq_len = input_audio.shape
-    dist, rank, world = _dist_info()
-    if world > 1 and seed is None:
-        # every rank steps a replica of the CMA-ES state and slices the same ask() batch: the replicas (and the
-        # find_w0 / random-crop draws) must be identical, so an unseeded run agrees on rank 0's draw of a seed
-        box = [int(np.random.SeedSequence().generate_state(1)[0] & 0x7FFFFFFF) if rank == 0 else None]
-        dist.broadcast_object_list(box, src=0)
-        seed = box[0]
+    _, rank, world = _dist_info()
+    seed = _agree_on_seed(seed)
     rng = np.random.RandomState(seed) if seed is not None else np.random
 
     # peak normalize (in place like the reference, 452-453)
-    input_audio /= torch.max(torch.abs(input_audio)).clamp(min=1e-8)
-    target_audio /= torch.max(torch.abs(target_audio)).clamp(min=1e-8)
+    _peak_normalize_(input_audio)
+    _peak_normalize_(target_audio)
 
     # compute target embedding (only once)
     target_embed = embed_func(target_audio, model, sample_rate)
@@ -360,8 +436,7 @@ def run_es(
     # never forwards it to process_audio, so the population is rendered without per-stage normalisation here too)
     evaluator = engine.PopulationEvaluator(input_audio, sample_rate, plugins, model, eval_targets, embed_func=eval_embed_func,
                                            entry_weights=entry_weights)
-    if evaluator.ndims != total_num_params:
-        raise ValueError(f"plugins declare {total_num_params} params, chain consumes {evaluator.ndims}")
+    total_num_params = _chain_dims(evaluator, plugins)
 
     def evaluate(W, dropout: float = 0.0, want_audio: bool = False, while_waiting=None):
         """GPU replacement of the reference's evaluate closure (474-573)."""
@@ -394,60 +469,29 @@ def run_es(
     init_param_dict = parameters_to_dict(w0, plugins)
     print(init_param_dict)
 
-    opts = {"bounds": [0, 1], "popsize": popsize}
-    if seed is not None:
-        opts["seed"] = seed
-    es = cma.CMAEvolutionStrategy(w0, sigma0, opts)
-
-    fval_history = []
-    wopt_history = []
-    iters_without_improvement = 0
-    n_evals = popsize if find_w0 else 0
+    run = _EsRun(w0, sigma0, popsize, seed)
+    run.n_evals = popsize if find_w0 else 0
 
     for iteration in range(max_iters):
-        W = es.ask()
+        W = run.ask()
         # (the next generation's normal deviates are drawn on the host while the GPU evaluates this one)
         fvals, output_embeds, output_audios = evaluate(
-            W, dropout=(dropout if (iteration + 1) < max_iters else 0.0), want_audio=savepop,
-            while_waiting=getattr(es, "prefetch", None))
-        n_evals += len(W)
-
-        # save best (pre-tell result, like the reference: index 0 is (None, inf))
-        wopt_history.append(es.result[0])
-        fval_history.append(es.result[1])
-
+            W, dropout=(dropout if (iteration + 1) < max_iters else 0.0), want_audio=savepop, while_waiting=run.es.prefetch)
         if savepop:
             savepop_to_disk(iteration, fvals, output_embeds, output_audios, run_dir, sample_rate,
                             first=shard_bounds(len(fvals), rank, world)[0])
-        es.tell(W, fvals)
+        stale = run.tell(fvals, iteration)
         if rank == 0:
-            es.disp()
-
-        # early stop (reference 655-670): an iteration counts as stale unless its best candidate beats the best value on
-        # record (the pre-tell history) by more than 0.01; the first iteration never counts
-        stale = iteration > 0 and min(fvals) - min(fval_history) > -0.01
-        iters_without_improvement = iters_without_improvement + 1 if stale else 0
+            run.es.disp()
         if stale and rank == 0:
-            print(f"Solution has not improved for {iters_without_improvement} iterations.")
-        if early_stop and iters_without_improvement > 10:
+            print(f"Solution has not improved for {run.stale} iterations.")
+        if early_stop and run.stale > 10:
             print("Stopping early due to no improvement.")
             break
 
-    wopt = es.result[0]
-    fopt = es.result[1]
-
     # render the current solution on the full (un-padded) input, like the reference (676-678)
-    output_audio = torch.from_numpy(process_audio(input_audio.squeeze(0).cpu().numpy(), wopt, sample_rate, plugins))
-    param_dict = parameters_to_dict(wopt, plugins)
-    return {
-        "output_audio": output_audio,
-        "params": param_dict,
-        "fopt": fopt,
-        "wopt": wopt,
-        "fval_history": fval_history,
-        "wopt_history": wopt_history,
-        "num_evals": n_evals,
-    }
+    output_audio = torch.from_numpy(process_audio(input_audio.squeeze(0).cpu().numpy(), run.es.result[0], sample_rate, plugins))
+    return run.result(output_audio, plugins)
 
 
 def run_staged_es(
@@ -486,13 +530,10 @@ def run_staged_es(
     if distance != "cosine":
         raise ValueError(f"Unknown distance: {distance}")
     savepop = bool(savepop or save_pop)
-    dist, rank, world = _dist_info()
-    if world > 1 and seed is None:
-        box = [int(np.random.SeedSequence().generate_state(1)[0] & 0x7FFFFFFF) if rank == 0 else None]
-        dist.broadcast_object_list(box, src=0)
-        seed = box[0]
-    input_audio /= torch.max(torch.abs(input_audio)).clamp(min=1e-8)
-    target_audio /= torch.max(torch.abs(target_audio)).clamp(min=1e-8)
+    _, rank, world = _dist_info()
+    seed = _agree_on_seed(seed)
+    _peak_normalize_(input_audio)
+    _peak_normalize_(target_audio)
     target_embed = embed_func(target_audio, model, sample_rate)
 
     names = list(plugins.keys())
@@ -504,15 +545,10 @@ def run_staged_es(
     for stage_idx in range(len(plugins)):
         stage_plugins = {k: plugins[k] for k in names[: stage_idx + 1]}
         print(f"Optimizing stage {stage_idx} ({list(stage_plugins.keys())})")
-        total_num_params = sum(p["num_params"] for p in stage_plugins.values())
         n_stage = plugins[names[stage_idx]]["num_params"]
         evaluator = engine.PopulationEvaluator(input_audio, sample_rate, stage_plugins, model, target_embed, embed_func=embed_func)
-        if evaluator.ndims != total_num_params:
-            raise ValueError(f"plugins declare {total_num_params} params, chain consumes {evaluator.ndims}")
-        opts = {"bounds": [0, 1], "popsize": popsize}
-        if seed is not None:
-            opts["seed"] = seed + stage_idx
-        es = cma.CMAEvolutionStrategy(np.ones(n_stage) * 0.5, sigma0, opts)
+        _chain_dims(evaluator, stage_plugins)
+        es = _EsRun.strategy(np.ones(n_stage) * 0.5, sigma0, popsize, None if seed is None else seed + stage_idx)
         for iteration in range(iters_per_stage):
             W = es.ask()
             if stage_idx > 0:
@@ -521,6 +557,8 @@ def run_staged_es(
                 W_stage = W
             fvals, _, output_audios = sharded_evaluate(W_stage, lambda Ws: evaluator.evaluate(Ws, want_audio=savepop))
             n_evals += len(W)
+            # run_optim.py 181-185: the histories hold the result AFTER tell and no stage stops early, so a stage steps the bare
+            # strategy and not an _EsRun with its pre-tell bookkeeping
             es.tell(W, fvals)
             if rank == 0:
                 es.disp()
@@ -544,17 +582,7 @@ def run_staged_es(
             from .audio_io import save_wav
 
             save_wav(os.path.join(run_dir, f"output_audio_stage_{stage_idx}.wav"), output_audio, sample_rate)
-    param_dict = parameters_to_dict(wopt_overall, plugins)
-    return {
-        "output_audio": output_audio,
-        "params": param_dict,
-        "fopt": fopt,
-        "wopt": wopt_overall,
-        "fval_history": fval_history,
-        "wopt_history": wopt_history,
-        "stage_wopts": stage_wopts,
-        "num_evals": n_evals,
-    }
+    return _es_result(output_audio, wopt_overall, fopt, fval_history, wopt_history, n_evals, plugins, stage_wopts=stage_wopts)
 
 
 def run_es_batch(
@@ -575,9 +603,9 @@ def run_es_batch(
 
     The reference optimises its examples one after the other (scripts/eval/eval_pst.py:691-765)
     and its evaluate closure assumes one input (style_transfer.py:520).  Here every pair keeps its
-    own CMA-ES state (seed + pair index) and each iteration evaluates the populations, stacked
-    pair-major as (B * popsize, D), in one pass over the GPU; pair b's candidates read input b and
-    are scored against target b.  Two forms of the call:
+    own CMA-ES trajectory (an _EsRun seeded seed + pair index, stepped exactly as run_es steps its one) and each iteration
+    evaluates the populations, stacked pair-major as (n * popsize, D), on the GPU; pair b's candidates read input b and
+    are scored against target b.  Two forms of the call, which differ only in how an iteration's populations reach the GPU:
 
     Tensors -- input_audios / target_audios (B, chs, seq_len), all pairs the same length and channel count.  One crop
     position per iteration, drawn from RandomState(seed), serves all pairs, and pairs that stop early (same rule as run_es,
@@ -591,69 +619,76 @@ def run_es_batch(
     when the rule needs none); pairs are grouped by evaluate-time length (engine.plan_ragged_groups: everything is 262144
     samples under random_crop or when the file is shorter) and every group is one GPU batch per iteration, its inputs cut
     out of one packed device buffer by stito_gather_crops; pairs that have stopped are no longer gathered, rendered or
-    embedded; the targets are embedded once, those of equal length in one call.  The bitwise promise above holds for this
-    form ALWAYS, `random_crop=True` on long inputs included.  The launches are eager (no graph replay).
+    embedded.  The bitwise promise above holds for this form ALWAYS, `random_crop=True` on long inputs included.  The
+    launches are eager (no graph replay).
 
-    Each pair is peak-normalised on its own, on clones: the caller's tensors are not modified.
-    Under torch.distributed the PAIRS are sharded over the ranks (no collective until
-    the final gather); every rank returns the full list of B result dicts."""
-    if isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple)):
-        return _run_es_batch_ragged(input_audios, target_audios, sample_rate, plugins, model, embed_func, max_iters, sigma0,
-                                    popsize, random_crop, seed, early_stop)
-    if input_audios.dim() != 3 or target_audios.dim() != 3 or input_audios.shape[0] != target_audios.shape[0]:
+    In both forms each pair is peak-normalised on its own, on clones: the caller's tensors are not modified; the targets are
+    embedded once, those of equal shape in one call, and a pair's target embedding is flattened to one row per entry (as the
+    evaluator flattens the candidates' embeddings), whatever shape embed_func gives it.  Under torch.distributed the PAIRS are
+    sharded over the ranks (no collective until the final gather); every rank returns the full list of B result
+    dicts.  An unseeded multi-rank
+    run agrees on rank 0's draw of a seed first, so that a pair's trajectory does not depend on the rank that owns it (an
+    unseeded run has no defined trajectory anyway, and a single-rank run enters no collective)."""
+    ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
+    if ragged:
+        input_audios, target_audios = _check_ragged_pairs(input_audios, target_audios)
+    elif input_audios.dim() != 3 or target_audios.dim() != 3 or input_audios.shape[0] != target_audios.shape[0]:
         raise ValueError("input_audios and target_audios must be (B, chs, seq_len) with the same B")
     dist, rank, world = _dist_info()
-    B_all = input_audios.shape[0]
+    seed = _agree_on_seed(seed)
+    B_all = len(input_audios)
     lo, hi = shard_bounds(B_all, rank, world)
     results = [None] * B_all
     if hi > lo:
-        xs = input_audios[lo:hi].clone()
-        ts = target_audios[lo:hi].clone()
-        B = hi - lo
-        total_num_params = sum([plugin["num_params"] for plugin in plugins.values()])
-        # peak normalise each pair on its own (run_es 452-453)
-        xs /= xs.abs().amax(dim=(1, 2), keepdim=True).clamp(min=1e-8)
-        ts /= ts.abs().amax(dim=(1, 2), keepdim=True).clamp(min=1e-8)
-        target_embed = embed_func(ts, model, sample_rate)
-        evaluator = engine.PopulationEvaluator(xs, sample_rate, plugins, model, target_embed, embed_func=embed_func)
-        if evaluator.ndims != total_num_params:
-            raise ValueError(f"plugins declare {total_num_params} params, chain consumes {evaluator.ndims}")
-        rng = np.random.RandomState(seed) if seed is not None else np.random
-        states = []
-        for b in range(B):
-            opts = {"bounds": [0, 1], "popsize": popsize}
-            if seed is not None:
-                opts["seed"] = seed + lo + b
-            states.append(dict(es=cma.CMAEvolutionStrategy(np.ones(total_num_params) * 0.5, sigma0, opts), fval_history=[],
-                               wopt_history=[], stale=0, active=True, last_W=None, n_evals=0))
+        if ragged:
+            xs = [a.detach().to("cpu", torch.float32).clone() for a in input_audios[lo:hi]]
+            ts = [a.detach().to("cpu", torch.float32).clone() for a in target_audios[lo:hi]]
+        else:
+            xs, ts = input_audios[lo:hi].clone(), target_audios[lo:hi].clone()
+        for a in (*xs, *ts):  # every pair on its own (run_es 452-453); the rows of a tensor are views of the clone
+            _peak_normalize_(a)
+        # target embeddings, once: targets of equal shape in one embed_func call
+        by_shape, rows = {}, [None] * len(ts)
+        for b, t in enumerate(ts):
+            by_shape.setdefault(tuple(t.shape), []).append(b)
+        for members in by_shape.values():
+            emb = embed_func(torch.stack([ts[b] for b in members]), model, sample_rate)
+            for k, b in enumerate(members):
+                rows[b] = {name: v.detach().reshape(len(members), -1)[k] for name, v in emb.items()}
+        target_embed = {name: torch.stack([row[name] for row in rows]) for name in rows[0]}
+
+        def make_evaluator(x, **kw):
+            return engine.PopulationEvaluator(x, sample_rate, plugins, model, target_embed, embed_func=embed_func, **kw)
+
+        def rng_of(s):  # unseeded: the global generator, not a fresh one
+            return np.random if s is None else np.random.RandomState(s)
+
+        pair_seeds = [None if seed is None else seed + lo + b for b in range(hi - lo)]  # CMA-ES and, in the list form, crops
+        if ragged:
+            evaluator, submit = _ragged_form(make_evaluator, xs, random_crop, [rng_of(s) for s in pair_seeds])
+        else:
+            evaluator, submit = _tensor_form(make_evaluator, xs, random_crop, rng_of(seed))
+        w0 = np.ones(_chain_dims(evaluator, plugins)) * 0.5
+        runs = [_EsRun(w0, sigma0, popsize, s) for s in pair_seeds]
         for iteration in range(max_iters):
-            if not any(st["active"] for st in states):
+            if not any(run.active for run in runs):
                 break
-            Ws = []
-            for st in states:
-                if st["active"]:
-                    st["last_W"] = st["es"].ask()
-                Ws.append(st["last_W"])
-            loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(W) for W in Ws], 0), random_crop=random_crop, rng=rng)
-            fv = loss.tolist()
-            for b, st in enumerate(states):
-                if not st["active"]:
-                    continue
-                fvals = fv[b * popsize:(b + 1) * popsize]
-                st["n_evals"] += popsize
-                st["wopt_history"].append(st["es"].result[0])
-                st["fval_history"].append(st["es"].result[1])
-                st["es"].tell(st["last_W"], fvals)
-                fval_delta = (min(fvals) - min(st["fval_history"])) if iteration > 0 else -0.02
-                st["stale"] = st["stale"] + 1 if fval_delta > -0.01 else 0
-                if early_stop and st["stale"] > 10:
-                    st["active"] = False
-        for b, st in enumerate(states):
-            wopt, fopt = st["es"].result[0], st["es"].result[1]
-            out = torch.from_numpy(process_audio(xs[b].cpu().numpy(), wopt, sample_rate, plugins))
-            results[lo + b] = {"output_audio": out, "params": parameters_to_dict(wopt, plugins), "fopt": fopt, "wopt": wopt,
-                               "fval_history": st["fval_history"], "wopt_history": st["wopt_history"],
-                               "num_evals": st["n_evals"]}
+            for run in runs:
+                if run.active:
+                    run.ask()
+            pending = submit(runs)  # [(pair indices, loss tensor)]: everything queued before any fitness is fetched
+            for run in runs:  # the next generation's normal deviates, drawn while the GPU works (as run_es does)
+                if run.active:
+                    run.es.prefetch()
+            for members, loss in pending:
+                fv = loss.tolist()
+                for k, b in enumerate(members):
+                    if runs[b].active:
+                        runs[b].tell(fv[k * popsize:(k + 1) * popsize], iteration)
+                        runs[b].active = not (early_stop and runs[b].stale > 10)
+        for b, run in enumerate(runs):
+            out = torch.from_numpy(process_audio(xs[b].cpu().numpy(), run.es.result[0], sample_rate, plugins))
+            results[lo + b] = run.result(out, plugins)
     if world > 1:
         gathered = [None] * world
         dist.all_gather_object(gathered, [(i, r) for i, r in enumerate(results) if r is not None])
@@ -661,6 +696,42 @@ def run_es_batch(
             for i, r in part:
                 results[i] = r
     return results
+
+
+def _tensor_form(make_evaluator, xs, random_crop, rng):
+    """-> (evaluator, submit) of run_es_batch's tensor form: ALL pairs every iteration, a stopped pair re-submitting its last
+    population -- the input buffer keeps its shape, so the evaluator's graph replay stays eligible -- and one crop position for
+    all, drawn by the evaluator from the one rng."""
+    evaluator = make_evaluator(xs)
+
+    def submit(runs):
+        loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(run.W) for run in runs], 0), random_crop=random_crop, rng=rng)
+        return [(range(len(runs)), loss)]
+
+    return evaluator, submit
+
+
+def _ragged_form(make_evaluator, xs, random_crop, rngs):
+    """-> (evaluator, submit) of run_es_batch's list form: per length group the ACTIVE pairs only, each with a crop position of
+    its own from its own rng, cut out of the packed inputs by one gather."""
+    ragged = engine.RaggedInputs(xs, engine._current_device())
+    # the evaluator never reads its own input on this path (every call brings its gathered buffer): a one-sample stand-in
+    evaluator = make_evaluator(torch.zeros((len(xs), xs[0].shape[0], 1)), use_graph=False)
+    groups = engine.plan_ragged_groups(ragged.lengths, random_crop)
+
+    def submit(runs):
+        pending = []
+        for eval_len, members in groups:  # one gather + one evaluate per group
+            act = [b for b in members if runs[b].active]
+            if not act:
+                continue
+            starts = [engine.crop_start(ragged.lengths[b], random_crop, rngs[b]) for b in act]
+            x = ragged.gather(act, starts, eval_len)
+            loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(runs[b].W) for b in act], 0), pairs=act, x=x)
+            pending.append((act, loss))
+        return pending
+
+    return evaluator, submit
 
 
 def _check_ragged_pairs(input_audios, target_audios):
@@ -686,97 +757,3 @@ def _check_ragged_pairs(input_audios, target_audios):
     if len({x.shape[0] for x in xs}) != 1:
         raise ValueError(f"inputs have mixed channel counts {[x.shape[0] for x in xs]}")
     return xs, ts
-
-
-def _run_es_batch_ragged(input_audios, target_audios, sample_rate, plugins, model, embed_func, max_iters, sigma0, popsize,
-                         random_crop, seed, early_stop):
-    """The list form of run_es_batch (see there)."""
-    xs_all, ts_all = _check_ragged_pairs(input_audios, target_audios)
-    dist, rank, world = _dist_info()
-    B_all = len(xs_all)
-    if world > 1 and seed is None:  # the ranks own different pairs, but a pair's seed must not depend on the sharding
-        box = [int(np.random.SeedSequence().generate_state(1)[0] & 0x7FFFFFFF) if rank == 0 else None]
-        dist.broadcast_object_list(box, src=0)
-        seed = box[0]
-    lo, hi = shard_bounds(B_all, rank, world)
-    results = [None] * B_all
-    if hi > lo:
-        B = hi - lo
-        total_num_params = sum([plugin["num_params"] for plugin in plugins.values()])
-
-        def normalised(a):  # run_es 452-453, on a float32 CPU clone
-            a = a.detach().to("cpu", torch.float32).clone()
-            a /= torch.max(torch.abs(a)).clamp(min=1e-8)
-            return a
-
-        xs = [normalised(a) for a in xs_all[lo:hi]]
-        ts = [normalised(a) for a in ts_all[lo:hi]]
-        # target embeddings, once: targets of equal shape in one embed_func call
-        by_shape, rows = {}, [None] * B
-        for b, t in enumerate(ts):
-            by_shape.setdefault(tuple(t.shape), []).append(b)
-        for members in by_shape.values():
-            emb = embed_func(torch.stack([ts[b] for b in members]), model, sample_rate)
-            for k, b in enumerate(members):
-                rows[b] = {name: v.detach().reshape(len(members), -1)[k] for name, v in emb.items()}
-        target_embed = {name: torch.stack([rows[b][name] for b in range(B)]) for name in rows[0]}
-        device = torch.device("cuda", torch.cuda.current_device())
-        ragged = engine.RaggedInputs(xs, device)
-        # the evaluator never reads its own input on this path (every call brings its gathered buffer): a one-sample stand-in
-        evaluator = engine.PopulationEvaluator(torch.zeros((B, xs[0].shape[0], 1)), sample_rate, plugins, model, target_embed,
-                                               embed_func=embed_func, use_graph=False)
-        if evaluator.ndims != total_num_params:
-            raise ValueError(f"plugins declare {total_num_params} params, chain consumes {evaluator.ndims}")
-        states = []
-        for b in range(B):
-            opts = {"bounds": [0, 1], "popsize": popsize}
-            if seed is not None:
-                opts["seed"] = seed + lo + b
-            states.append(dict(es=cma.CMAEvolutionStrategy(np.ones(total_num_params) * 0.5, sigma0, opts), fval_history=[],
-                               wopt_history=[], stale=0, active=True, W=None, n_evals=0,
-                               rng=np.random.RandomState(seed + lo + b) if seed is not None else np.random))
-        groups = engine.plan_ragged_groups(ragged.lengths, random_crop)
-        for iteration in range(max_iters):
-            if not any(st["active"] for st in states):
-                break
-            for st in states:
-                if st["active"]:
-                    st["W"] = st["es"].ask()
-            pending = []
-            for eval_len, members in groups:  # one gather + one evaluate per group, queued before any fitness is fetched
-                act = [b for b in members if states[b]["active"]]
-                if not act:
-                    continue
-                starts = [engine.crop_start(ragged.lengths[b], random_crop, states[b]["rng"]) for b in act]
-                x = ragged.gather(act, starts, eval_len)
-                loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(states[b]["W"]) for b in act], 0), pairs=act, x=x)
-                pending.append((act, loss))
-            for st in states:  # the next generation's normal deviates, drawn while the GPU works (as run_es does)
-                if st["active"]:
-                    st["es"].prefetch()
-            for act, loss in pending:
-                fv = loss.tolist()
-                for k, b in enumerate(act):
-                    st = states[b]
-                    fvals = fv[k * popsize:(k + 1) * popsize]
-                    st["n_evals"] += popsize
-                    st["wopt_history"].append(st["es"].result[0])
-                    st["fval_history"].append(st["es"].result[1])
-                    st["es"].tell(st["W"], fvals)
-                    stale = iteration > 0 and min(fvals) - min(st["fval_history"]) > -0.01
-                    st["stale"] = st["stale"] + 1 if stale else 0
-                    if early_stop and st["stale"] > 10:
-                        st["active"] = False
-        for b, st in enumerate(states):
-            wopt, fopt = st["es"].result[0], st["es"].result[1]
-            out = torch.from_numpy(process_audio(xs[b].numpy(), wopt, sample_rate, plugins))
-            results[lo + b] = {"output_audio": out, "params": parameters_to_dict(wopt, plugins), "fopt": fopt, "wopt": wopt,
-                               "fval_history": st["fval_history"], "wopt_history": st["wopt_history"],
-                               "num_evals": st["n_evals"]}
-    if world > 1:
-        gathered = [None] * world
-        dist.all_gather_object(gathered, [(i, r) for i, r in enumerate(results) if r is not None])
-        for part in gathered:
-            for i, r in part:
-                results[i] = r
-    return results

@@ -51,6 +51,36 @@ def test_crop_start_draw_sequence_interleaves_with_pairs_that_draw_nothing():
     assert crop_start(CROP + MARGIN + 1, True, np.random.RandomState(0)) == MARGIN
 
 
+@pytest.mark.parametrize("n", LENGTHS)
+@pytest.mark.parametrize("random_crop", [False, True])
+@pytest.mark.parametrize("parallel", [False, True])
+def test_evaluator_input_is_crop_start_and_eval_length(n, random_crop, parallel):
+    """PopulationEvaluator._input (CPU tensors: the method only slices and pads) against the two pure functions on a twin
+    generator: the same samples, and the same NUMBER of draws -- afterwards the generators are in the same state."""
+    from st_ito.engine import PopulationEvaluator, crop_start, eval_length
+    x = torch.arange(2 * n, dtype=torch.float32).reshape(1, 2, n)
+    ev = object.__new__(PopulationEvaluator)
+    ev.x_full, ev._x_padded = x, None
+    rng, twin = np.random.RandomState(3), np.random.RandomState(3)
+    outs = []
+    for _ in range(3):
+        got = ev._input(random_crop, rng, parallel)
+        outs.append(got)
+        if parallel:                                   # the pool branch: the input as it is, nothing drawn
+            assert got is x
+        else:
+            s, length = crop_start(n, random_crop, twin), eval_length(n, random_crop)
+            want = x[..., s:s + length]
+            want = torch.nn.functional.pad(want, (0, length - want.shape[-1]))
+            assert got.shape == want.shape and torch.equal(got, want) and got.is_contiguous()
+        a, b = rng.get_state(), twin.get_state()
+        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+    if not parallel and n < CROP:
+        assert outs[0] is outs[1] is outs[2]           # padded once: a captured graph reads the buffer by address
+    if not parallel and (n == CROP or (n > CROP and not random_crop)):
+        assert outs[0] is x                            # returned as it is, without a copy
+
+
 def test_eval_length_and_group_planner():
     from st_ito.engine import eval_length, plan_ragged_groups
     for n in LENGTHS:
