@@ -58,10 +58,6 @@ static constexpr int W23_PLANE = 51;                        // 3 x 17 pixels of 
 static constexpr int W23_ENTRY = 4 * 4 * W23_PLANE * 16;    // bytes of one k-step of the patch: [quad][plane][51][16 B]
 static constexpr int W23_RING = 6;  // k-step entries: the four of the group being read + two in flight (see conv_wino23r_body.inc)
 
-#ifndef W23_ABL
-#define W23_ABL 0  // timing-experiment bit mask (1 no transform, 2 no MFMAs, 4 no DMA, 8 no epilogue, 16 no Z exchange); 0 in every build that ships
-#endif
-
 // power-of-two scale of a stream's transformed input: |B^T d B| <= 4 max|d|, amax < 2^e -> 2^(12 - e): below 2^14
 __host__ __device__ __forceinline__ float w23_vscale(unsigned amax_bits) {
     int e = (int)((amax_bits >> 23) & 0xff) - 126;  // amax = f * 2^e, f in [0.5, 1)
@@ -242,8 +238,8 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
 // channel quad Q_ of k-step KS_ of the group prepared last -> ring entry E_ (< 2 W23_RING): one masked 1 KB copy; the lanes of the
 // plane without a pixel get zeros
 #define W23_DMA_Q(KS_, E_, Q_)                                                                                   \
-    if (!(W23_ABL & 4)) {                                                                                        \
-        const char *sb_ = dma_base + (int64_t)(2 * (KS_) + ((Q_) >> 1)) * plane8 + ((Q_) & 1) * 16;               \
+    {                                                                                                            \
+        const char *sb_ = dma_base + (int64_t)(2 * (KS_) + ((Q_) >> 1)) * plane8 + ((Q_) & 1) * 16; \
         const int eo_ = W23_ENT(E_) * W23_ENTRY + (Q_) * 4 * W23_PLANE * 16;                                     \
         uint64_t keep_;                                                                                          \
         asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"              \
@@ -301,7 +297,7 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
         if (rok_) {                                                                                              \
             const char *sb_ = mel_sb_ + (rg_ * g.W + 32 * (C_).txb - 2) * 4;   /* 32-bit inside a stream */      \
             uint64_t keep_;                                                                                      \
-            asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"             \
+            asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t" \
                          "global_load_lds_dword %1, %2\n\ts_mov_b64 exec, %0"                                    \
                          : "=&s"(keep_) : "v"(mel_voff), "s"(sb_), "s"(lds0 + (unsigned)(mr_ - smem)), "s"(mel_cm_) : "memory"); \
         }                                                                                                        \
@@ -342,8 +338,8 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
 // lo' hi, hi' lo, hi' hi (the large term last) on ONE accumulator, one product per block of the main stream (a product that
 // follows the one it accumulates on directly waits for it)
 #define W23_C1_MM(P_)                                                                                            \
-    if ((P_) == 0) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c1acc) : "v"(c1wl), "v"(__builtin_bit_cast(rh8, c1bh)));            \
-    else if ((P_) == 1) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c1acc) : "v"(c1wh), "v"(__builtin_bit_cast(rh8, c1bl)));       \
+    if ((P_) == 0) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c1acc) : "v"(c1wl), "v"(__builtin_bit_cast(rh8, c1bh))); \
+    else if ((P_) == 1) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c1acc) : "v"(c1wh), "v"(__builtin_bit_cast(rh8, c1bl))); \
     else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c1acc) : "v"(c1wh), "v"(__builtin_bit_cast(rh8, c1bh)));
 #define W23_C1_DRAIN() asm volatile("s_nop 15\n\ts_nop 7" : "+v"(c1acc));
 // ReLU as a signed-integer max on the bit patterns (no canonicalising instruction in front of it), then the four register quads
@@ -376,18 +372,6 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
     f32x4 dA[2], dB[2];            // patch rows a1 / a2 in flight
     float vtmp[4];
     const char *pa = ring, *pb = ring;
-    if (W23_ABL & 1) {   // timing experiments only: constant operands / accumulators in place of the ablated producers
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { bhv[j] = (ru4)(0x3c003c00u); blv[j] = (ru4)(0u); }
-    }
-    if (W23_ABL & 2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int n = 0; n < NB; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[j][n][r] = 0.0f;
-    }
 
     // ---- epilogue of a group (cD: the group before the one being multiplied): this wave's NB register quads of the outputs -----
     bool e_have = false;
@@ -407,15 +391,13 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
     }
 // 1 / (u_scale v_scale(stream)) = u_inv * 2^(e - 12): both powers of two, so the exponents add (integer arithmetic on scalars)
 #define W23_E_BEGIN()                                                                                            \
-    if (!(W23_ABL & 8)) {                                                                                        \
-        if (cD.s != e_esc_s) {                                                                                   \
-            e_esc_s = cD.s;                                                                                      \
-            e_esc_bits = u_inv_bits + 0x3f800000u - __float_as_uint(w23_vscale_s(g.amax_in[cD.s]));              \
-        }                                                                                                        \
-        if (cD.s != mx_s) { W23_AMAX_FLUSH() mx = 0; mx_s = cD.s; }                                              \
-    }
+    if (cD.s != e_esc_s) {                                                                                       \
+        e_esc_s = cD.s;                                                                                          \
+        e_esc_bits = u_inv_bits + 0x3f800000u - __float_as_uint(w23_vscale_s(g.amax_in[cD.s]));                  \
+    }                                                                                                            \
+    if (cD.s != mx_s) { W23_AMAX_FLUSH() mx = 0; mx_s = cD.s; }
 #define W23_E_SETUP(K_)                                                                                          \
-    if (!(W23_ABL & 8)) {                                                                                        \
+    {                                                                                                            \
         const int u_ = wv * NB + (K_), n_ = u_ >> 2, rq_ = u_ & 3;                                               \
         ex = xch + ((n_ * 4 + rq_) * 64 + lane) * 16;                                                            \
         const int cl_ = 32 * n_ + 8 * rq_ + 4 * half;                                                            \
@@ -424,13 +406,13 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
         e_co8 = cb * 4 * NB + 4 * n_ + rq_;                                                                      \
     }
 #define W23_E_LD(C_)                                                                                             \
-    if (!(W23_ABL & 8)) {                                                                                        \
+    {                                                                                                            \
         _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) Zr[i_] = *(const f32x4 *)(ex + ((i_ * 2 + (C_)) * NB * 4 * 64) * 16); \
     }
 // Y[0][c] = relu(bn(Z0 + Z1 + Z2)), Y[1][c] = relu(bn(Z1 - Z2 - Z3)): per channel pair six packed instructions in ONE asm
 // statement (no compiler s_nop between dependent statements), then eight v_max (asm: the compiler canonicalises in front of its own)
 #define W23_E_Y(C_)                                                                                              \
-    if (!(W23_ABL & 8)) {                                                                                        \
+    {                                                                                                            \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) {                                                       \
             f32x2 t0_, t1_;                                                                                      \
             asm volatile("v_pk_add_f32 %2, %4, %5\n\tv_pk_add_f32 %3, %5, %6 neg_lo:[0,1] neg_hi:[0,1]\n\t"      \
@@ -447,7 +429,7 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
 #define W23_MAX4(V_) max(max(__float_as_uint((V_)[0]), __float_as_uint((V_)[1])), max(__float_as_uint((V_)[2]), __float_as_uint((V_)[3])))
 #define W23_Y4(R_, C_) __builtin_shufflevector(Yk[R_][C_][0], Yk[R_][C_][1], 0, 1, 2, 3)
 #define W23_E_ST(K_)                                                                                             \
-    if (!(W23_ABL & 8)) {                                                                                        \
+    {                                                                                                            \
         if (POOL) {                                                                                              \
             const int64_t ob_ = ((((int64_t)cD.s * (g.Cout >> 3) + e_co8) * g.Ho + 2 * cD.band) * g.Wo + 16 * cD.txb) * 8; \
             f32x2 p_[2];                                                                                         \
@@ -479,21 +461,19 @@ __global__ __launch_bounds__(W23_THREADS) void k_conv_wino23r(const float *__res
 #define W23_ACC2(J_, N_, R_) ((f32x2){acc[J_][N_][R_], acc[J_][N_][(R_) + 1]})
 #define W23_ZSTORE()                                                                                             \
     W23_STAMP(8)                                                                                                 \
-    if (!(W23_ABL & 16)) {                                                                                       \
-        asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[3][0]), "+v"(acc[3][1])); \
-        _Pragma("unroll") for (int n_ = 0; n_ < NB; ++n_)                                                        \
-            _Pragma("unroll") for (int rq_ = 0; rq_ < 4; ++rq_) {                                                \
-                f32x2 z0_[2], z1_[2];                                                                            \
-                _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                 \
-                    asm volatile("v_pk_add_f32 %0, %2, %3\n\tv_pk_add_f32 %1, %3, %4 neg_lo:[0,1] neg_hi:[0,1]\n\t" \
-                                 "v_pk_add_f32 %0, %0, %4\n\tv_pk_add_f32 %1, %1, %5 neg_lo:[0,1] neg_hi:[0,1]"  \
-                                 : "=&v"(z0_[h_]), "=&v"(z1_[h_])                                                \
-                                 : "v"(W23_ACC2(0, n_, 4 * rq_ + 2 * h_)), "v"(W23_ACC2(1, n_, 4 * rq_ + 2 * h_)), \
-                                   "v"(W23_ACC2(2, n_, 4 * rq_ + 2 * h_)), "v"(W23_ACC2(3, n_, 4 * rq_ + 2 * h_))); \
-                *(f32x4 *)(xch + ((((wv * 2 + 0) * NB + n_) * 4 + rq_) * 64 + lane) * 16) = __builtin_shufflevector(z0_[0], z0_[1], 0, 1, 2, 3); \
-                *(f32x4 *)(xch + ((((wv * 2 + 1) * NB + n_) * 4 + rq_) * 64 + lane) * 16) = __builtin_shufflevector(z1_[0], z1_[1], 0, 1, 2, 3); \
-            }                                                                                                    \
-    }                                                                                                            \
+    asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[3][0]), "+v"(acc[3][1])); \
+    _Pragma("unroll") for (int n_ = 0; n_ < NB; ++n_)                                                            \
+        _Pragma("unroll") for (int rq_ = 0; rq_ < 4; ++rq_) {                                                    \
+            f32x2 z0_[2], z1_[2];                                                                                \
+            _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                     \
+                asm volatile("v_pk_add_f32 %0, %2, %3\n\tv_pk_add_f32 %1, %3, %4 neg_lo:[0,1] neg_hi:[0,1]\n\t" \
+                             "v_pk_add_f32 %0, %0, %4\n\tv_pk_add_f32 %1, %1, %5 neg_lo:[0,1] neg_hi:[0,1]"      \
+                             : "=&v"(z0_[h_]), "=&v"(z1_[h_])                                                    \
+                             : "v"(W23_ACC2(0, n_, 4 * rq_ + 2 * h_)), "v"(W23_ACC2(1, n_, 4 * rq_ + 2 * h_)), \
+                               "v"(W23_ACC2(2, n_, 4 * rq_ + 2 * h_)), "v"(W23_ACC2(3, n_, 4 * rq_ + 2 * h_))); \
+            *(f32x4 *)(xch + ((((wv * 2 + 0) * NB + n_) * 4 + rq_) * 64 + lane) * 16) = __builtin_shufflevector(z0_[0], z0_[1], 0, 1, 2, 3); \
+            *(f32x4 *)(xch + ((((wv * 2 + 1) * NB + n_) * 4 + rq_) * 64 + lane) * 16) = __builtin_shufflevector(z1_[0], z1_[1], 0, 1, 2, 3); \
+        }                                                                                                        \
     W23_STAMP(9)                                                                                                 \
     W23_BARRIER()                                                                                                \
     W23_STAMP(10)

@@ -42,7 +42,6 @@
 
 namespace stito {
 
-#ifndef W43_ABL
 #ifndef W43_CLK
 #define W43_CLK 0  // measurement build (tools/ab_build.sh clk -DW43_CLK=1): the workgroup in the middle of the grid reads s_memtime (shader
                    // clock) and s_memrealtime (constant 100 MHz) at its start and end, the launcher prints the ratio = the clock the part
@@ -61,8 +60,6 @@ namespace stito {
 #else
 #define W43_CLK_BEGIN()
 #define W43_CLK_END()
-#endif
-#define W43_ABL 0  // timing-experiment bit mask (1 no transform, 2 no U copies, 4 no patch copies, 8 no operand reads); 0 in every build that ships
 #endif
 static constexpr int W43_THREADS = 512;
 static constexpr int W43_K = 4;                          // input channels per chunk
@@ -651,9 +648,9 @@ __global__ __launch_bounds__(W43_THREADS, MODE >= 2 ? 4 : 2) void k_conv_wino43(
 // S0 holds group 2 of the previous chunk on entry; the sets alternate S0, S1, S0 and the next period starts on S1.
 // MORE: chunk k+1 exists -- its production (U copies, transform) and the patch copy of chunk k+2 are spread over the first
 // MFMA gaps; patch(c) lives in buffer c % 2.
-#define W43_OPS(X) if (!VOUT && !(W43_ABL & 8)) { X }
-#define W43_UCP(X) if (!VOUT && MORE_ && !(W43_ABL & 2)) { X }
-#define W43_TRF(X) if (!PREV && MORE_ && !(W43_ABL & 1)) { X }
+#define W43_OPS(X) if (!VOUT) { X }
+#define W43_UCP(X) if (!VOUT && MORE_) { X }
+#define W43_TRF(X) if (!PREV && MORE_) { X }
 #define W43_PERIOD4(P2, G0, G1, N2, FIRST, MORE)                                                                 \
     {                                                                                                   \
         constexpr bool MORE_ = MORE;                                                                     \
@@ -662,7 +659,7 @@ __global__ __launch_bounds__(W43_THREADS, MODE >= 2 ? 4 : 2) void k_conv_wino43(
         const float *pb_r = patch0 + ((k + 1) & 1) * PFL;     /* patch(k+1); patch(k+2) goes where patch(k) was */ \
         if (V16) W43_STORE_V16(k, cur) else if (V16B) W43_STORE_V16B(k, cur) else if (V16C) W43_STORE_V16C(k, cur) else if (VOUT) W43_STORE_V(k, cur) \
         if (!(FIRST)) {                                                                                  \
-            W43_GAP(P2, 2, 0, 0, if (MORE_ && !(W43_ABL & 4)) { if (PREV) { W43_COPY_V1(k + 1, nxt, 0) } else W43_COPY_P(k + 2, k & 1) }) \
+            W43_GAP(P2, 2, 0, 0, if (MORE_) { if (PREV) { W43_COPY_V1(k + 1, nxt, 0) } else W43_COPY_P(k + 2, k & 1) }) \
             W43_GAP(P2, 2, 1, 0, W43_OPS(W43_LOAD_OPS(G0, sb, 0)) W43_UCP(W43_COPY_U1(k + 1, nxt, 0)))   \
             W43_GAP(P2, 2, 2, 0, W43_UCP(W43_COPY_U1(k + 1, nxt, 1)))                                    \
             W43_GAP(P2, 2, 0, 1, W43_UCP(W43_COPY_U1(k + 1, nxt, 2)))                                    \
@@ -753,9 +750,6 @@ __global__ void k_pack_wino43(const float *__restrict__ w, int Cout, int Cin, fl
         }
 }
 
-#ifndef S43B_ABL
-#define S43B_ABL 0  // timing experiment (k_conv_wino43s / s2): 1 = no main loop (prologue + epilogue(s) only), 2 = no slab copies in the loop, 4 = no operand reads / MFMAs; 0 in every build that ships
-#endif
 // ---- split-precision streaming convolution ----------------------------------------------------------------------------
 // The same convolution as MODE 1 (transformed input and weights both streamed), on the f16 matrix pipe: every f32 operand x
 // is carried as two f16 halves  hi = rn16(s x), lo = rn16(s x - hi)  (s a power of two: per layer for the weights, per
@@ -819,15 +813,12 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s(const char *__rest
 // issued in order, in the way of the wave's own MFMAs.  vw / uw = the wave's first piece of either part.
 #define S43_ISSUE(SL, BUF) S43_ISSUE_R(SL, BUF, 0, 12)
 #define S43_MFMA(Q, A_, B_) acc[Q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_, B_, acc[Q], 0, 0, 0);
-// S43_ILV (default): the period as a fixed interleave, one piece per MFMA gap (sched_barrier between gaps, every MFMA pinned:
+// The period as a fixed interleave, one piece per MFMA gap (sched_barrier between gaps, every MFMA pinned:
 // DESIGN.md 4.1(4)): at most two operand reads between two MFMAs (the rate at which tools/ubench/mfma_interleave.hip shows
 // them free) instead of the whole period's reads at its top behind the barrier, the last block of a slab multiplied at the top
 // of the NEXT period from registers (ahP ..) while that period's first reads are in flight, and the issuing set's copies in
 // three groups between products instead of ahead of them.  Measured (conv_bench, 512 streams): the five two-sweep layers
 // 13.07 -> 12.64 ms, profiles/README.md.
-#ifndef S43_ILV
-#define S43_ILV 1
-#endif
 #define S43_MFMA_P(Q, A_, B_) asm volatile("" : "+v"(acc[Q])); S43_MFMA(Q, A_, B_) asm volatile("" : "+v"(acc[Q]));
 #define S43_GAP() __builtin_amdgcn_sched_barrier(0);
 #define S43_ISSUE_R(SL, BUF, C0_, C1_)                                                                   \
@@ -839,35 +830,22 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s(const char *__rest
 #define S43_PERIOD(K18, SL)                                                                              \
     {                                                                                                    \
         constexpr int BUF_ = (K18) % 3, NB_ = ((K18) + 2) % 3;                                            \
-        constexpr int Q0_ = (2 * ((K18) % 9)) % 9, Q1_ = (2 * ((K18) % 9) + 1) % 9;                       \
+        constexpr int Q0_ = (2 * ((K18) % 9)) % 9;   /* block 0 of this period */                         \
         constexpr int QP_ = (2 * (((K18) + 8) % 9) + 1) % 9;   /* block 1 of the period before */         \
         const bool mine_ = set == ((K18) & 1);                                                            \
-        const bool iss_ = !(S43B_ABL & 2) && mine_ && (SL) + 2 < n_slabs;                                 \
+        const bool iss_ = mine_ && (SL) + 2 < n_slabs;                                                    \
         const char *pa_ = a_rd + BUF_ * S43_SLAB, *pb_ = b_rd + BUF_ * S43_SLAB;                          \
-        if (!S43_ILV) {                                                                                   \
-            if (iss_) { S43_ISSUE((SL) + 2, NB_) }                                                        \
-            const h8 ah0 = *(const h8 *)(pa_), al0 = *(const h8 *)(pa_ + 1024);                           \
-            const h8 bh0 = *(const h8 *)(pb_), bl0 = *(const h8 *)(pb_ + 2048);                           \
-            const h8 ah1 = *(const h8 *)(pa_ + 2048), al1 = *(const h8 *)(pa_ + 3072);                    \
-            const h8 bh1 = *(const h8 *)(pb_ + 4096), bl1 = *(const h8 *)(pb_ + 6144);                    \
-            if (!(S43B_ABL & 4)) {                                                                        \
-            S43_MFMA(Q0_, al0, bh0) S43_MFMA(Q1_, al1, bh1)                                               \
-            S43_MFMA(Q0_, ah0, bl0) S43_MFMA(Q1_, ah1, bl1)                                               \
-            S43_MFMA(Q0_, ah0, bh0) S43_MFMA(Q1_, ah1, bh1)                                               \
-            }                                                                                             \
-        } else if (!(S43B_ABL & 4)) {                                                                     \
-            h8 ah0, al0, bh0, bl0;                                                                        \
-            const bool prev_ = (SL) > 0;                                                                  \
-            S43_GAP()                                                                                     \
-            if (prev_) { S43_MFMA_P(QP_, alP, bhP) } ah0 = *(const h8 *)(pa_); al0 = *(const h8 *)(pa_ + 1024); S43_GAP() \
-            if (prev_) { S43_MFMA_P(QP_, ahP, blP) } bh0 = *(const h8 *)(pb_); bl0 = *(const h8 *)(pb_ + 2048); \
-                if (iss_) { S43_ISSUE_R((SL) + 2, NB_, 0, 4) } S43_GAP()                                  \
-            if (prev_) { S43_MFMA_P(QP_, ahP, bhP) } ahP = *(const h8 *)(pa_ + 2048); alP = *(const h8 *)(pa_ + 3072); S43_GAP() \
-            S43_MFMA_P(Q0_, al0, bh0) bhP = *(const h8 *)(pb_ + 4096); blP = *(const h8 *)(pb_ + 6144);   \
-                if (iss_) { S43_ISSUE_R((SL) + 2, NB_, 4, 8) } S43_GAP()                                  \
-            S43_MFMA_P(Q0_, ah0, bl0) if (iss_) { S43_ISSUE_R((SL) + 2, NB_, 8, 12) } S43_GAP()           \
-            S43_MFMA_P(Q0_, ah0, bh0) S43_GAP()                                                           \
-        } else if (iss_) { S43_ISSUE((SL) + 2, NB_) }                                                     \
+        h8 ah0, al0, bh0, bl0;                                                                            \
+        const bool prev_ = (SL) > 0;                                                                      \
+        S43_GAP()                                                                                         \
+        if (prev_) { S43_MFMA_P(QP_, alP, bhP) } ah0 = *(const h8 *)(pa_); al0 = *(const h8 *)(pa_ + 1024); S43_GAP() \
+        if (prev_) { S43_MFMA_P(QP_, ahP, blP) } bh0 = *(const h8 *)(pb_); bl0 = *(const h8 *)(pb_ + 2048); \
+            if (iss_) { S43_ISSUE_R((SL) + 2, NB_, 0, 4) } S43_GAP()                                      \
+        if (prev_) { S43_MFMA_P(QP_, ahP, bhP) } ahP = *(const h8 *)(pa_ + 2048); alP = *(const h8 *)(pa_ + 3072); S43_GAP() \
+        S43_MFMA_P(Q0_, al0, bh0) bhP = *(const h8 *)(pb_ + 4096); blP = *(const h8 *)(pb_ + 6144);       \
+            if (iss_) { S43_ISSUE_R((SL) + 2, NB_, 4, 8) } S43_GAP()                                      \
+        S43_MFMA_P(Q0_, ah0, bl0) if (iss_) { S43_ISSUE_R((SL) + 2, NB_, 8, 12) } S43_GAP()               \
+        S43_MFMA_P(Q0_, ah0, bh0) S43_GAP()                                                               \
         if (!mine_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                      \
         W43_BARRIER()                                                                                     \
     }
@@ -875,15 +853,13 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s(const char *__rest
     if (set == 0) { S43_ISSUE(0, 0) } else { S43_ISSUE(1, 1) }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     W43_BARRIER()
-    h8 ahP, alP, bhP, blP;  // S43_ILV: operands of the previous period's second block
-    for (int sl = 0; sl < ((S43B_ABL & 1) ? 0 : n_slabs); sl += 18) {  // Cin % 64 == 0
+    h8 ahP, alP, bhP, blP;  // operands of the previous period's second block
+    for (int sl = 0; sl < n_slabs; sl += 18) {  // Cin % 64 == 0
         S43_PERIOD(0, sl) S43_PERIOD(1, sl + 1) S43_PERIOD(2, sl + 2) S43_PERIOD(3, sl + 3) S43_PERIOD(4, sl + 4) S43_PERIOD(5, sl + 5)
         S43_PERIOD(6, sl + 6) S43_PERIOD(7, sl + 7) S43_PERIOD(8, sl + 8) S43_PERIOD(9, sl + 9) S43_PERIOD(10, sl + 10) S43_PERIOD(11, sl + 11)
         S43_PERIOD(12, sl + 12) S43_PERIOD(13, sl + 13) S43_PERIOD(14, sl + 14) S43_PERIOD(15, sl + 15) S43_PERIOD(16, sl + 16) S43_PERIOD(17, sl + 17)
     }
-    if (S43_ILV && !(S43B_ABL & 5)) {  // the last period's second block (n_slabs % 18 == 0: accumulator 8)
-        S43_MFMA_P(8, alP, bhP) S43_MFMA_P(8, ahP, blP) S43_MFMA_P(8, ahP, bhP)
-    }
+    S43_MFMA_P(8, alP, bhP) S43_MFMA_P(8, ahP, blP) S43_MFMA_P(8, ahP, bhP)  // the last period's second block (n_slabs % 18 == 0: accumulator 8)
     w43_epilogue<TTW, POOL, true>(smem, acc, tid, pg, nh, g, n0, vtr0, tc0, scale, shift, out, u_inv_p[0], amax);
     W43_CLK_END()
 }
@@ -944,13 +920,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s2(const char *__res
 
     f32x16 acc[9];
 #define S43B_ISSUE(SL, BUF) S43B_ISSUE_R(SL, BUF, 0, 12)
-#define S43B_BLOCK(T_, Q_)                                                                               \
-    {                                                                                                    \
-        const h8 ah_ = *(const h8 *)(pa_ + (T_) * 8192), al_ = *(const h8 *)(pa_ + (T_) * 8192 + 2048);   \
-        const h8 bh_ = *(const h8 *)(pb_ + (T_) * 8192), bl_ = *(const h8 *)(pb_ + (T_) * 8192 + 2048);   \
-        S43_MFMA(Q_, al_, bh_) S43_MFMA(Q_, ah_, bl_) S43_MFMA(Q_, ah_, bh_)                              \
-    }
-// S43_ILV as in k_conv_wino43s: block 2 of a slab waits in registers for the next period
+// the fixed interleave of k_conv_wino43s: block 2 of a slab waits in registers for the next period
 #define S43B_ISSUE_R(SL, BUF, C0_, C1_) /* piece = 4 c + w4 as in k_conv_wino43s: c < 6 input, else weights */ \
     _Pragma("unroll") for (int c_ = (C0_); c_ < (C1_); ++c_) {                                            \
         const char *src_ = c_ < 6 ? vw + (int64_t)(SL) * S43B_PART + c_ * 4096                            \
@@ -963,25 +933,20 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s2(const char *__res
     {                                                                                                    \
         constexpr int BUF_ = (K6) % 3, NB_ = ((K6) + 2) % 3, SUB_ = (K6) % 3, QP_ = 3 * (((K6) + 2) % 3) + 2; \
         const bool mine_ = set == ((K6) & 1);                                                             \
-        const bool iss_ = !(S43B_ABL & 2) && mine_ && (SL) + 2 < n_slabs;                                 \
+        const bool iss_ = mine_ && (SL) + 2 < n_slabs;                                                    \
         const char *pa_ = a_rd + BUF_ * S43B_SLAB, *pb_ = b_rd + BUF_ * S43B_SLAB;                        \
-        if (!S43_ILV) {                                                                                   \
-            if (iss_) { S43B_ISSUE((SL) + 2, NB_) }                                                       \
-            if (!(S43B_ABL & 4)) { S43B_BLOCK(0, 3 * SUB_) S43B_BLOCK(1, 3 * SUB_ + 1) S43B_BLOCK(2, 3 * SUB_ + 2) } \
-        } else if (!(S43B_ABL & 4)) {                                                                     \
-            h8 ah0, al0, bh0, bl0, ah1, al1, bh1, bl1;                                                    \
-            const bool prev_ = (SL) > 0;                                                                  \
-            S43_GAP()                                                                                     \
-            if (prev_) { S43_MFMA_P(QP_, alP, bhP) } S43B_LDA(0, ah0, al0) S43_GAP()                       \
-            if (prev_) { S43_MFMA_P(QP_, ahP, blP) } S43B_LDB(0, bh0, bl0) S43_GAP()                       \
-            if (prev_) { S43_MFMA_P(QP_, ahP, bhP) } S43B_LDA(1, ah1, al1) if (iss_) { S43B_ISSUE_R((SL) + 2, NB_, 0, 4) } S43_GAP() \
-            S43_MFMA_P(3 * SUB_, al0, bh0) S43B_LDB(1, bh1, bl1) S43_GAP()                                \
-            S43_MFMA_P(3 * SUB_, ah0, bl0) S43B_LDA(2, ahP, alP) if (iss_) { S43B_ISSUE_R((SL) + 2, NB_, 4, 8) } S43_GAP() \
-            S43_MFMA_P(3 * SUB_, ah0, bh0) S43B_LDB(2, bhP, blP) S43_GAP()                                \
-            S43_MFMA_P(3 * SUB_ + 1, al1, bh1) if (iss_) { S43B_ISSUE_R((SL) + 2, NB_, 8, 12) } S43_GAP()  \
-            S43_MFMA_P(3 * SUB_ + 1, ah1, bl1) S43_GAP()                                                  \
-            S43_MFMA_P(3 * SUB_ + 1, ah1, bh1) S43_GAP()                                                  \
-        } else if (iss_) { S43B_ISSUE((SL) + 2, NB_) }                                                    \
+        h8 ah0, al0, bh0, bl0, ah1, al1, bh1, bl1;                                                        \
+        const bool prev_ = (SL) > 0;                                                                      \
+        S43_GAP()                                                                                         \
+        if (prev_) { S43_MFMA_P(QP_, alP, bhP) } S43B_LDA(0, ah0, al0) S43_GAP()                          \
+        if (prev_) { S43_MFMA_P(QP_, ahP, blP) } S43B_LDB(0, bh0, bl0) S43_GAP()                          \
+        if (prev_) { S43_MFMA_P(QP_, ahP, bhP) } S43B_LDA(1, ah1, al1) if (iss_) { S43B_ISSUE_R((SL) + 2, NB_, 0, 4) } S43_GAP() \
+        S43_MFMA_P(3 * SUB_, al0, bh0) S43B_LDB(1, bh1, bl1) S43_GAP()                                    \
+        S43_MFMA_P(3 * SUB_, ah0, bl0) S43B_LDA(2, ahP, alP) if (iss_) { S43B_ISSUE_R((SL) + 2, NB_, 4, 8) } S43_GAP() \
+        S43_MFMA_P(3 * SUB_, ah0, bh0) S43B_LDB(2, bhP, blP) S43_GAP()                                    \
+        S43_MFMA_P(3 * SUB_ + 1, al1, bh1) if (iss_) { S43B_ISSUE_R((SL) + 2, NB_, 8, 12) } S43_GAP()     \
+        S43_MFMA_P(3 * SUB_ + 1, ah1, bl1) S43_GAP()                                                      \
+        S43_MFMA_P(3 * SUB_ + 1, ah1, bh1) S43_GAP()                                                      \
         if (!mine_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                      \
         W43_BARRIER()                                                                                     \
     }
@@ -1029,14 +994,12 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s2(const char *__res
         if (set == 0) { S43B_ISSUE(0, 0) } else { S43B_ISSUE(1, 1) }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         W43_BARRIER()
-        h8 ahP, alP, bhP, blP;  // S43_ILV: operands of the previous slab's block 2
-        for (int sl = 0; sl < ((S43B_ABL & 1) ? 0 : n_slabs); sl += 6) {  // Cin % 32 == 0
+        h8 ahP, alP, bhP, blP;  // operands of the previous slab's block 2
+        for (int sl = 0; sl < n_slabs; sl += 6) {  // Cin % 32 == 0
             S43B_PERIOD(0, sl) S43B_PERIOD(1, sl + 1) S43B_PERIOD(2, sl + 2)
             S43B_PERIOD(3, sl + 3) S43B_PERIOD(4, sl + 4) S43B_PERIOD(5, sl + 5)
         }
-        if (S43_ILV && !(S43B_ABL & 5)) {  // the last slab's block 2 (n_slabs % 6 == 0: local row 2 -> accumulator 8)
-            S43_MFMA_P(8, alP, bhP) S43_MFMA_P(8, ahP, blP) S43_MFMA_P(8, ahP, bhP)
-        }
+        S43_MFMA_P(8, alP, bhP) S43_MFMA_P(8, ahP, blP) S43_MFMA_P(8, ahP, bhP)  // the last slab's block 2 (n_slabs % 6 == 0: local row 2 -> accumulator 8)
         if (SWSPLIT && sweep == 1) {   // the partner's partial outputs have to be there (and visible) before they are read
             if (tid == 0)
                 while (__hip_atomic_load(sweep_flags + b, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(8);
@@ -1152,9 +1115,6 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s2(const char *__res
 // tiles): a lane's accumulator quad = 4 consecutive couts of ITS tile, 16-byte partial-sum accesses and stores fall out.
 // The arithmetic and its order are k_conv_wino43s2's -- per position the same sequence of products, Y = A^T M A with the same
 // association -- so the two kernels return identical bits (tested): stito_cnn14_forward may pick either by batch size.
-#ifndef S43C_ABL
-#define S43C_ABL 0  // timing experiment (k_conv_wino43s3): 1 = no epilogues, 2 = no main loops, 4 = no partial stores, 8 = no partial loads; 0 in every build that ships
-#endif
 __device__ __forceinline__ const char *w43_uniform(const char *p) {
     const uint64_t v = (uint64_t)(uintptr_t)p;
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
@@ -1257,7 +1217,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
         // the six rows' slabs follow one another in both streams: ONE stream of 6 nP periods, the ring keeps filling through the
         // epilogues (which touch neither LDS nor barriers); nP % 2 == 0; the ring position is a run-time value (three loop bodies
         // for it cost registers)
-        for (int sl = sweep * nP; sl < ((S43C_ABL & 2) ? 0 : (sweep + 1) * nP); sl += 2) {
+        for (int sl = sweep * nP; sl < (sweep + 1) * nP; sl += 2) {
             S43C_PERIOD(0, sl, buf)
             buf = buf == 2 ? 0 : buf + 1;
             S43C_PERIOD(1, sl + 1, buf)
@@ -1266,13 +1226,6 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
         // ---- this row's column combination Z[c] = sum_j M[row][j] A[j][c] (c = 0..3) goes to the scratch area (rows 0..4: stores
         // only, nothing waits for them); the sweep of row 5 reads the five others back, one output column at a time, and finishes:
         // Y[r][c] = sum_i A[i][r] Z_i[c],  A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1] ------------------------------
-        if (S43C_ABL & 1) {   // (timing builds: keep the accumulators alive)
-            float s_ = 0.f;
-#pragma unroll
-            for (int q = 0; q < 12; ++q) s_ += acc[q][0] + acc[q][7] + acc[q][15];
-            if (s_ == 12345.f) out[tid] = s_;
-            continue;
-        }
 #define S43C_Z(BLK, GQ, Z_)   /* element by element straight from the accumulator registers (vector temporaries of them are copies) */ \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                   \
             const float m0 = acc[0 + (BLK)][4 * (GQ) + e], m1 = acc[2 + (BLK)][4 * (GQ) + e], m2 = acc[4 + (BLK)][4 * (GQ) + e], \
@@ -1291,10 +1244,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
                 S43C_Z(bg >> 2, bg & 3, Z)
                 f32x4 *pt = my_partial + bg * (5 * 4 * 64);   // [row 0..4][c][lane]
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (S43C_ABL & 4) { if (Z[c][0] == 12345.f) pt[(sweep * 4 + c) * 64] = Z[c]; }   // timing builds: no partial stores
-                    else pt[(sweep * 4 + c) * 64] = Z[c];
-                }
+                for (int c = 0; c < 4; ++c) pt[(sweep * 4 + c) * 64] = Z[c];
             }
             if (SWSPLIT) {   // publish this row: every thread's stores, then the count
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1322,7 +1272,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
 #pragma unroll
                 for (int i = 0; i < 5; ++i)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) zr[i][c] = (S43C_ABL & 8) ? Zl[bg][c] : pt[(i * 4 + c) * 64];   // (timing builds: no partial loads)
+                    for (int c = 0; c < 4; ++c) zr[i][c] = pt[(i * 4 + c) * 64];
                 const int co = ct * 128 + cq * 32 + 8 * gq + 4 * oct;
                 f32x4 sc = *(const f32x4 *)(scale + co);
                 const f32x4 sh = *(const f32x4 *)(shift + co);

@@ -155,10 +155,10 @@ __global__ void k_prepare(ChainArgs chain, const double *__restrict__ w, int P, 
 // ------------------------------------------------------------------------------------------------
 // Parametric EQ
 // ------------------------------------------------------------------------------------------------
-#ifndef EQ_NC_BUILD
-#define EQ_NC_BUILD 256
-#endif
-static constexpr int EQ_NC = EQ_NC_BUILD;  // time chunks per stream == threads per workgroup
+// time chunks per stream == threads per workgroup.  Measured against 512 and 1 024 (profiles/round6_eq_nc_ab.txt): 512 wins 8 % while a
+// stream has a CU to itself and loses 15 % at the bench shape (one 512-thread workgroup per CU instead of three 256-thread ones), 1 024
+// spills; the chunk boundaries set the float64 rounding, so the count cannot depend on the batch
+static constexpr int EQ_NC = 256;
 static constexpr int EQ_TS = 32;   // samples per LDS tile row (= tile floats per thread)
 static constexpr int EQ_NG = EQ_NC / 32;   // 32-lane groups of the workgroup: a group stages one 32-sample row of the tile at a time
 
@@ -472,9 +472,6 @@ __device__ __forceinline__ float rv_dpp(float v) {
 __device__ __forceinline__ float rv_mix(float wet_own, float wet_other, float x, float wet1, float wet2, float dry) {
     return fmaf(wet_own, wet1, fmaf(wet_other, wet2, x * dry));
 }
-#ifndef RV_ABL
-#define RV_ABL 0   // timing builds only (tools/reverb_ablate.sh): 1 = comb role idle, 2 = all-pass role idle
-#endif
 
 // HALF (round 6, small populations: a population of 32 puts 32 of these workgroups on 256 CUs): one workgroup per (candidate, CHANNEL)
 // -- the channel's eight combs on two waves, its all-pass chain on three, the same staging (the comb input is the sum of both
@@ -510,7 +507,7 @@ __global__ __launch_bounds__(RV_THREADS) void k_reverb(InView in, float *__restr
 
     if (wv < NCW) {
         // ---- comb role: the four 16-lane rows of wave w are combs 4 w .. 4 w + 3 (HALF: of this workgroup's channel); lane l of a row owns samples 12 l .. 12 l + 11.
-        // The kernel is bound by the instructions its waves issue between two barriers, summed per SIMD (tools/reverb_ablate.sh: the
+        // The kernel is bound by the instructions its waves issue between two barriers, summed per SIMD (builds with one role idle, DESIGN.md 4.2: the
         // roles' times ADD -- barriers only 0.4 ms, + all-pass 0.4, + comb 0.7 at 256 candidates -- at ~4.8 cycles per instruction and
         // SIMD): with two combs of 32 lanes x 6 samples per wave (rounds 2 - 4) the eight comb waves issued 8 x 92 instructions per
         // tile; a row per comb halves the waves for ~100 each, and the scan needs no step across rows.
@@ -541,7 +538,6 @@ __global__ __launch_bounds__(RV_THREADS) void k_reverb(InView in, float *__restr
         for (int k = 0; k <= ntiles; ++k) {
             RV_BARRIER();
             if (k == ntiles) break;
-            if (RV_ABL & 1) continue;
             const float *in_c = s_in + (k & 1) * RV_TT + RV_RUN * cl;
             float *cmb = s_comb + (k & 1) * RV_CB + cidx * RV_TT + (cidx >= 8 ? RV_PAD : 0) + RV_RUN * cl;
             float pq[RV_RUN], w[RV_RUN];
@@ -604,7 +600,7 @@ __global__ __launch_bounds__(RV_THREADS) void k_reverb(InView in, float *__restr
         int64_t t_out = -(int64_t)RV_TT + t2;
         for (int k = 0; k <= ntiles; ++k) {
             RV_BARRIER();
-            if (k >= 1 && !(RV_ABL & 2)) {
+            if (k >= 1) {
                 const float *cmb = s_comb + ((k - 1) & 1) * RV_CB + c2 * (8 * RV_TT + RV_PAD) + t2;
                 float cs[8], bv[4];
                 float *abp[4];

@@ -237,13 +237,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_logmel(FrontendDev fe, const flo
 // spectrum goes to the wave's LDS buffer and the mel / log / norm stage is the one of k_logmel (same order of sums).  Nothing
 // is shared between waves: LDS operations of one wave execute in order, so no barrier is needed anywhere.
 // ------------------------------------------------------------------------------------------------------------------------
-#ifndef FW_ABL
-#define FW_ABL 0  // timing experiment (1 no mel stage, 2 no FFT passes, 4 no unpack); 0 in every build that ships
-#endif
-#ifndef FW_FRAMES
-#define FW_FRAMES 4
-#endif
-static constexpr int FW_F = FW_FRAMES;               // consecutive frames per wave
+static constexpr int FW_F = 4;                       // consecutive frames per wave: five hop loads for four frames, where a frame on its own takes two
 static constexpr int FW_ROW = 66;                    // float2 per row of the first transpose (64 + 2: lanes (k1, a) of a half-wave on 32 distinct bank pairs)
 static constexpr int FW_WAVE_F2 = 16 * FW_ROW + 64;  // float2 per wave: transpose buffer (>= 1 024 + 1 floats of power spectrum), w64 twiddles
 static constexpr int FW_MAX_MELS = 256;
@@ -285,10 +279,8 @@ __device__ __forceinline__ float2 fw_tw(const float2 *__restrict__ table, int t)
 }
 #define FW_LDS_SYNC() { __builtin_amdgcn_wave_barrier(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 
-#ifndef FW_OCC
-#define FW_OCC 3
-#endif
-__global__ __launch_bounds__(FE_THREADS, FW_OCC) void k_logmel_wave(FrontendDev fe, const float *__restrict__ audio,
+static constexpr int FW_WG_PER_CU = 3;  // = waves per SIMD (168 VGPRs): the kernel is latency-bound, 1.45 ms against 1.87 at two waves per SIMD
+__global__ __launch_bounds__(FE_THREADS, FW_WG_PER_CU) void k_logmel_wave(FrontendDev fe, const float *__restrict__ audio,
                                                              const float *__restrict__ peaks, int norm_passes, int C,
                                                              int64_t L, int64_t T, float *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -391,7 +383,6 @@ __global__ __launch_bounds__(FE_THREADS, FW_OCC) void k_logmel_wave(FrontendDev 
                 const float2 v = j < 8 ? (c == 0 ? hm0[j] : hs0[j]) : (c == 0 ? hm1[j - 8] : hs1[j - 8]);
                 x[j] = make_float2(v.x * w.x, v.y * w.y);
             }
-            if (!(FW_ABL & 2)) {
             fw_dft16(x);
             buf[lane] = x[FW_K(0)];
 #pragma unroll
@@ -418,12 +409,9 @@ __global__ __launch_bounds__(FE_THREADS, FW_OCC) void k_logmel_wave(FrontendDev 
                 x[q] = a0; x[q + 4] = a1; x[q + 8] = a2; x[q + 12] = a3;
             }
             FW_LDS_SYNC()
-            }
             // ---- unpack the real transform (as k_logmel), power spectrum into the wave's buffer ---------------------------
             float *pw = (float *)buf;
             const int pl = (64 - lane) & 63;
-            if (FW_ABL & 4) { for (int m = 0; m < 16; ++m) pw[lane + 64 * m] = x[m].x; }
-            else
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
                 const int k = lane + 64 * m;
@@ -447,8 +435,6 @@ __global__ __launch_bounds__(FE_THREADS, FW_OCC) void k_logmel_wave(FrontendDev 
             }
             FW_LDS_SYNC()
             // ---- mel bands, 10 log10(clamp(., 1e-10)), input norm: four lanes per band (k_logmel's order of sums) ---------
-            if (FW_ABL & 1) { if (lane < M) out[((int64_t)(cand * C + c) * T + t) * M + lane] = pw[lane * 8]; if (lane + 64 < M) out[((int64_t)(cand * C + c) * T + t) * M + lane + 64] = pw[lane * 8 + 4]; }
-            else
             for (int q0 = 0; q0 < 4 * M; q0 += 64) {
                 const int q = q0 + lane;
                 const bool live = q < 4 * M;

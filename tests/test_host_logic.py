@@ -562,19 +562,29 @@ def test_bench_self_launches_ranks_dryrun():
     assert bad.returncode != 0 and "WORLD_SIZE=1" in (bad.stderr + bad.stdout)
 
 
+def _shipped_device_asm(name, tmp_path):
+    """Device assembly of st-ito_amd/csrc/<name>.hip under the flags the Makefile gives build/<name>.o -- CXXFLAGS and any
+    per-object additions (-ffp-contract=off for compressor.hip) -- read from make's own dry run, not restated here."""
+    import shlex
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    csrc = os.path.join(ROOT, "st-ito_amd", "csrc")
+    dry = subprocess.run(["make", "-n", "-B", f"build/{name}.o", f"HIPCC={hipcc}"], cwd=csrc, capture_output=True, text=True, check=True).stdout
+    cmds = [shlex.split(l) for l in dry.splitlines() if f"{name}.hip" in l]
+    assert len(cmds) == 1 and cmds[0][0] == hipcc and cmds[0][-4:] == ["-c", f"{name}.hip", "-o", f"build/{name}.o"], dry
+    out = tmp_path / f"{name}.s"
+    subprocess.check_call(cmds[0][:-4] + ["-S", "--cuda-device-only", "-w", f"{name}.hip", "-o", str(out)], cwd=csrc)
+    return out.read_text()
+
+
 def test_compressor_scan_ring_registers_are_out_of_the_compilers_reach(tmp_path):
     """k_comp_blockscan keeps its 32-block register ring and the in-flight loads in fixed VGPRs v100+ across separate asm
     statements (generated: tools/gen/gen_comp_scan_asm.py); those registers are only declared as clobbers, so nothing tells
     the compiler they are live in between.  Build check: the code hipcc itself emits for that kernel -- everything
     outside the asm statements -- must stay below v100."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "st-ito_amd", "csrc", "compressor.hip")
-    out = tmp_path / "comp.s"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-w", src, "-o", str(out)])
-    text = out.read_text()
+    text = _shipped_device_asm("compressor", tmp_path)
     m = re.search(r"^(_ZN5stito16k_comp_blockscan\w*):.*?^\s*s_endpgm", text, flags=re.S | re.M)
     assert m, "k_comp_blockscan not found in the compiled assembly"
     body, inside, highest, n_asm = m.group(0), False, -1, 0
@@ -599,15 +609,7 @@ def test_reverb_staging_ring_registers_are_out_of_the_compilers_reach(tmp_path):
     compiler could legally copy a register whose load was still in flight).  The registers are only declared as clobbers, so --
     as for the compressor scan's ring -- the build check is that everything hipcc itself emits for the kernel stays below v64,
     that the ring's 36 loads are all inside asm statements, and that the kernel does not spill."""
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "st-ito_amd", "csrc", "dsp.hip")
-    out = tmp_path / "dsp.s"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-w",
-                           "-I", os.path.join(ROOT, "include"), src, "-o", str(out)])
-    text = out.read_text()
+    text = _shipped_device_asm("dsp", tmp_path)
     bodies = [m.group(0) for m in re.finditer(r"^(_ZN5stito8k_reverb\w*):.*?^\s*s_endpgm", text, flags=re.S | re.M)]
     assert len(bodies) == 2, "k_reverb<false> and k_reverb<true> (one workgroup per candidate / per channel) expected in the compiled assembly"
     highest = -1

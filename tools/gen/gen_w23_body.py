@@ -31,12 +31,14 @@ halves alternating so that consecutive blocks never chain on one accumulator):
                        1..3 are still dead, so that its temporaries cost no registers;
   after phase 3: the accumulators drain, Z_i of this group go to the exchange buffer, barrier.
 
-    python tools/gen/gen_w23_body.py > st-ito_amd/csrc/conv_wino23r_body.inc"""
+The three committed files, one command each (tests/test_generated_sources.py holds them to these outputs byte for byte):
+
+    python tools/gen/gen_w23_body.py          > st-ito_amd/csrc/conv_wino23r_body.inc
+    python tools/gen/gen_w23_body.py fuse1    > st-ito_amd/csrc/conv_wino23r_body_f1.inc
+    python tools/gen/gen_w23_body.py prologue > st-ito_amd/csrc/conv_wino23r_pro.inc"""
 import sys
 
-NB = 2
 DMA_STEP = 1   # blocks between two copies (measured at 512 streams, conv_block1.conv2: 1 -> 5.40 ms, 4 -> 5.73 ms: the copies need the time to land, not a lower issue rate)
-NO_T = NO_M = False   # ablation variants (W23_ABL & 1: no transform instructions, & 2: no products)
 FUSE = False          # "fuse1" variant: the patch is not copied, it is COMPUTED -- relu(bn1(conv3x3(log-mel))) on the matrix pipe -- in the copy slots
 VCOMB = {0: (0, 2, "sub"), 1: (1, 2, "add"), 2: (2, 1, "sub"), 3: (1, 3, "sub")}   # V(i, j) = t[a] -+ t[c]
 
@@ -48,7 +50,6 @@ class Asm:
     def inp(self, name, cons, expr): self.inps.append((name, cons, expr)); return "%[" + name + "]"
     def add(self, s): self.ins.append(s)
     def emit(self, indent="        "):
-        if not self.ins: return indent + "/* (ablated) */"
         body = "\\n\\t".join(self.ins)
         o = ", ".join(f'[{n}] "{c}"({e})' for n, c, e in self.outs)
         i = ", ".join(f'[{n}] "{c}"({e})' for n, c, e in self.inps)
@@ -57,7 +58,6 @@ class Asm:
 def mfma(a, j, n, p, ks):
     """product p of position j, channel half n: lo' hi, hi' lo, hi' hi (the large term last); the first product of a group
     starts the accumulator from the inline constant 0"""
-    if NO_M: return
     w = f"Wt[{j}][{ks}][{n}][{1 if p == 0 else 0}]"
     b = f"W23_BL({j})" if p == 1 else f"W23_BH({j})"
     wa, ba = a.inp("w", "a", w), a.inp("b", "v", b)
@@ -70,7 +70,6 @@ def mfma(a, j, n, p, ks):
 
 def unit(a, q, j, sv):
     """B operand registers 2 q, 2 q + 1 of position j (hi and lo halves) from t[q]: 12 instructions"""
-    if NO_T: return
     ta, tc, op = VCOMB[j]
     s = a.inp("sv", "s", sv)
     v = [a.out(f"v{e}", "=&v", f"vtmp[{e}]") for e in range(4)]
@@ -91,7 +90,6 @@ def unit(a, q, j, sv):
 
 def tcomb(a, q, b):
     """t[q][b] = d[a1][b] + sg d[a2][b]: two packed fmas on the load buffer b & 1"""
-    if NO_T: return
     sg = a.inp("sg", "v", "sg2")
     for h in range(2):
         t = a.out(f"t{h}", "=&v", f"tt[{q}][{b}][{h}]")   # early clobber: the second fma still reads its inputs
@@ -111,7 +109,6 @@ def phase(ks, out):
         pre, post = [], []
         a = Asm()
         mfma(a, j, n, p, ks)
-        guard = None
         if s < 12 and s % 2 == 0:
             uj, uq = UNITS[s // 2]
             unit(a, uq, uj, "sv")
@@ -149,7 +146,7 @@ def phase(ks, out):
         if s == 10: nxt_pre.append(f"W23_SETP(ent + {ks + 1})")
         if 10 <= s <= 17:
             q, b = ORDER[s - 10]
-            nxt_post = None if NO_T else f"W23_LD({q}, {b})"
+            nxt_post = f"W23_LD({q}, {b})"
         else:
             nxt_post = None
         if 12 <= s <= 19:
@@ -163,11 +160,7 @@ def phase(ks, out):
         # (the last phase works ahead for the NEXT group; behind the last group that work runs on stale LDS contents and is never
         # used -- cheaper than a branch around it, which would also make hipcc copy the accumulators between the two arms)
         if nxt_pre: lines.append(" ".join(nxt_pre))
-        if guard:   # the last phase works ahead for the NEXT group: without one, only the product
-            b_ = Asm(); mfma(b_, j, n, p, ks)
-            lines.append(f"if ({guard}) {{\n" + a.emit("            ") + "\n        } else {\n" + b_.emit("            ") + "\n        }")
-        else:
-            lines.append(a.emit().lstrip())
+        lines.append(a.emit().lstrip())
         if nxt_post: lines.append(nxt_post)
         lines += post
         out.append(f"        /* {ks}.{s:2d} */ " + "\n        ".join(lines) + "\n        W23_FENCE()")
@@ -177,7 +170,7 @@ def body(proto):
     if proto:
         # t and the position-0 operands of the first group's first k-step (no products yet)
         for q, b in ORDER:
-            if not NO_T: out.append(f"    W23_LD({q}, {b})")
+            out.append(f"    W23_LD({q}, {b})")
             a = Asm(); tcomb(a, q, b); out.append(a.emit("    "))
         for q in range(2):
             a = Asm(); unit(a, q, 0, "sv"); out.append(a.emit("    "))
@@ -193,9 +186,5 @@ def body(proto):
 
 proto = "prologue" in sys.argv[1:]
 FUSE = "fuse1" in sys.argv[1:]
-print("// GENERATED by tools/gen/gen_w23_body.py -- do not edit (NB = 2, 4 k-steps per group; the W23_ABL & 3 variants are timing experiments)")
-for abl in range(4):
-    NO_T, NO_M = bool(abl & 1), bool(abl & 2)
-    print(("#if" if abl == 0 else "#elif") + f" (W23_ABL & 3) == {abl}")
-    print("\n".join(body(proto)))
-print("#endif")
+print("// GENERATED by tools/gen/gen_w23_body.py" + "".join(" " + a for a in sys.argv[1:]) + " -- do not edit (4 k-steps per group)")
+print("\n".join(body(proto)))

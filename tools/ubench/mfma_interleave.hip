@@ -182,7 +182,7 @@ static void run_fed(int nm, float *out, long long *res_d) {
            R, D, DEP, PAT ? "kernel addresses" : "lane * 16", MW, (double)(hi - lo) / ((double)nm * MW));
 }
 
-// PHASE: the streaming convolutions' period as it is compiled (S43_ILV), in asm: 9 MFMAs in three dependent triples per wave and
+// PHASE: the streaming convolutions' period as it is compiled (the fixed interleave of S43_PERIOD), in asm: 9 MFMAs in three dependent triples per wave and
 // barrier, 12 operand reads in the first six gaps, the first triple fed from the phase before.  BAR = 0: without the s_barrier.
 template <int MW, int BAR, int DATA = 0>
 __global__ __launch_bounds__(256 * MW) void kphase(int nphase, float *out, long long *res) {
