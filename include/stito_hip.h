@@ -57,7 +57,23 @@ enum {
     STITO_FX_CHORUS = 7,        /* effects.py:962-985 (pedalboard.Chorus = juce::dsp::Chorus<float>), 5 params (rate_hz is declared and,
                                    as in the reference's process(), not passed on: 1 Hz), 1-channel; aux_dev / aux_len: the LFO table
                                    of stito_chorus_lfo, at least n_samples long */
-    STITO_FX_NUM_KINDS = 8
+    /* The reference's second effect family, apply_parametric_eq / apply_compressor / apply_distortion (effects.py:545-706):
+     * dasp_pytorch.functional.parametric_eq / compressor / distortion.  dasp-pytorch is an un-vendored, un-pinned dependency:
+     * the three stages are restated from the library's published algorithm, PARITY UNPINNED (ABI 10.2). */
+    STITO_FX_DASP_EQ = 8,       /* effects.py:651-706, 18 params (gain -18..18 dB, frequency 20..20 000 Hz, Q 0.1..10 for low shelf,
+                                   four peaking sections, high shelf; RBJ, normalised by a0).  Applied as the library's sosfilt_via_fsm:
+                                   H = prod rfft(b, N) / rfft(a, N), N = 2^ceil(log2(2 n - 1)), y = irfft(rfft(x, N) H)[:n], i.e.
+                                   CIRCULAR filtering over N -- evaluated as the float64 recursion started from the periodic state
+                                   (I - A^N)^-1 A^(N-n) s_n, coefficients in float64.  The library's own float32 evaluation is
+                                   ill-conditioned at low cutoffs (0.3 of peak at 20 Hz / Q 10) and is not the target. */
+    STITO_FX_DASP_COMPRESSOR = 9, /* effects.py:623-648, 6 params (threshold -60..0 dB, ratio 1..20, attack 0.1..250 ms, release
+                                   10..2000 ms -- consumed and, as in the library, unused --, knee 1..24 dB, make-up 0..24 dB),
+                                   lookahead_samples = 512: the signal path is delayed by 512 samples (zeros in front), the gain is
+                                   not.  Side chain = sum of the channels the signal has at that point, one gain for all of them; the
+                                   stage never up-mixes, whatever num_channels says.  The one-pole smoother is frequency-sampled
+                                   like the EQ: started from a^(N-n) g_n / (1 - a^N). */
+    STITO_FX_DASP_DISTORTION = 10, /* effects.py:545-555, 1 param (drive 0..48 dB): tanh(x 10^(drive/20)) */
+    STITO_FX_NUM_KINDS = 11
 };
 
 #define STITO_MAX_FX_PARAMS 32
@@ -91,7 +107,8 @@ const char *stito_last_error(void);
  * STITO_CONV_WINOGRAD_F4_SPLIT3; 10: stito_cnn14_weights.chunk_* (appended), stito_conv_timing_read_tagged). */
 int stito_version(void);
 /* Additions since the last change of stito_version() that leave every existing symbol and struct as it is (a caller built against
- * 10.0 runs unchanged): 1 = stito_gather_crops. */
+ * 10.0 runs unchanged): 1 = stito_gather_crops; 2 = STITO_FX_DASP_EQ, _DASP_COMPRESSOR, _DASP_DISTORTION (kinds 8 - 10 of
+ * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits). */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi

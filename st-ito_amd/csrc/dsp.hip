@@ -47,7 +47,11 @@ __constant__ double c_pmin[STITO_FX_NUM_KINDS][STITO_MAX_FX_PARAMS] = {
     {0, 0, 0, 0},
     {-48},
     {0},
-    {0.1, 0.1, 0, 0, 0}};
+    {0.1, 0.1, 0, 0, 0},
+    // dasp family, effects.py:659-681 (EQ), 629-634 (compressor), 551 (distortion)
+    {-18, 20, 0.1, -18, 20, 0.1, -18, 20, 0.1, -18, 20, 0.1, -18, 20, 0.1, -18, 20, 0.1},
+    {-60, 1, 0.1, 10, 1, 0},
+    {0}};
 __constant__ double c_pmax[STITO_FX_NUM_KINDS][STITO_MAX_FX_PARAMS] = {
     {24, 4000, 4, 24, 10000, 4, 24, 10000, 4, 24, 10000, 4, 24, 10000, 4, 24, 18000, 4},
     {0, 20, 100, 1000},
@@ -56,8 +60,11 @@ __constant__ double c_pmax[STITO_FX_NUM_KINDS][STITO_MAX_FX_PARAMS] = {
     {1, 1, 1, 1},
     {48},
     {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1},
-    {10, 20, 1, 1, 1}};
-static const int h_nparams[STITO_FX_NUM_KINDS] = {18, 4, 2, 3, 4, 1, 25, 5};
+    {10, 20, 1, 1, 1},
+    {18, 20000, 10, 18, 20000, 10, 18, 20000, 10, 18, 20000, 10, 18, 20000, 10, 18, 20000, 10},
+    {0, 20, 250, 2000, 24, 24},
+    {48}};
+static const int h_nparams[STITO_FX_NUM_KINDS] = {18, 4, 2, 3, 4, 1, 25, 5, 18, 6, 1};
 
 struct ChainArgs {
     int n_fx;
@@ -107,14 +114,14 @@ __global__ void k_prepare(ChainArgs chain, const double *__restrict__ w, int P, 
     const stito_fx_desc &fx = chain.fx[f];
     const int kind = fx.kind;
     double v[STITO_MAX_FX_PARAMS];
-    const int np = kind == 0 ? 18 : kind == 1 ? 4 : kind == 2 ? 2 : kind == 3 ? 3 : kind == 4 ? 4 : kind == 5 ? 1 : kind == 6 ? 25 : 5;
+    const int np = kind == 0 ? 18 : kind == 1 ? 4 : kind == 2 ? 2 : kind == 3 ? 3 : kind == 4 ? 4 : kind == 5 ? 1 : kind == 6 ? 25 : kind == 7 ? 5 : kind == 8 ? 18 : kind == 9 ? 6 : 1;
     for (int p = 0; p < np; ++p) {
         const double raw = ((fx.fixed_mask >> p) & 1u) ? fx.fixed_raw[p]
                                                        : w[(int64_t)cand * D + fx.w_offset + fx.has_bypass + p];
         v[p] = __dadd_rn(__dmul_rn(raw, c_pmax[kind][p] - c_pmin[kind][p]), c_pmin[kind][p]);
     }
     double *o = coef + ((int64_t)f * P + cand) * COEF_STRIDE;
-    if (kind == STITO_FX_PARAMETRIC_EQ) {
+    if (kind == STITO_FX_PARAMETRIC_EQ || kind == STITO_FX_DASP_EQ) {  // dasp's biquad() is the same RBJ cookbook, float64 here
         for (int s = 0; s < 6; ++s) rbj(v[3 * s], v[3 * s + 1], v[3 * s + 2], sr, s == 0 ? 0 : (s == 5 ? 2 : 1), o + 5 * s);
     } else if (kind == STITO_FX_COMPRESSOR) {  // juce::dsp::Compressor<float>::update + BallisticsFilter (juce_comp.h)
         juce_compressor_coef(v[0], v[1], v[2], v[3], sr, o);
@@ -147,7 +154,16 @@ __global__ void k_prepare(ChainArgs chain, const double *__restrict__ w, int P, 
             o[12 + b] = (float)v[12 + b] * 10.0f + 1.0f;
         }
         o[24] = (float)v[24];
-    } else {
+    } else if (kind == STITO_FX_DASP_COMPRESSOR) {
+        // dasp compressor(): alpha_A = exp(-log(9) / (fs attack_ms / 1000)), a float32 tensor in the library.  Evaluated in float64 and
+        // rounded to float32 ONCE, so that a host restatement lands on the same float32 (float32 exp / log of two libraries may differ
+        // by an ulp, and an ulp of a coefficient next to 1 is 3e-4 of a 250 ms time constant).  release_ms = v[3] is unused, as there.
+        o[0] = (float)v[0];
+        o[1] = (float)v[1];
+        o[2] = (float)exp(-log(9.0) / (sr * (v[2] / 1e3)));
+        o[3] = (float)v[4];
+        o[4] = (float)v[5];
+    } else {  // Gain, dasp distortion: 10^(dB / 20)
         o[0] = powf(10.0f, (float)v[0] / 20.0f);
     }
 }
@@ -176,8 +192,17 @@ __device__ __forceinline__ double eq_step(double x, const EqSec (&c)[6], double 
     return x;
 }
 
-__global__ __launch_bounds__(EQ_NC) void k_eq(InView in, PostOp post, float *__restrict__ out, int64_t out_cand_stride,
-                                               int C, int64_t L, const double *__restrict__ coef) {
+// PERIODIC (STITO_FX_DASP_EQ): dasp's sosfilt_via_fsm multiplies the spectrum of x by H = prod rfft(b, N) / rfft(a, N) on
+// N = 2^ceil(log2(2 L - 1)) points -- circular filtering over N, whose first L samples are this same recursion started from the
+// state s* that the zero-padded signal leaves behind once it has gone round: s* = A^(N - L) s_L + A^N s*, i.e.
+//     s* = (I - A^N)^-1 A^(N - L) s_L,      s_L = the zero-state state after the L samples.
+// Pass A and the chunk scan give s_L (taken at T = the end of the last chunk that holds samples, which steps on through zeros:
+// A^(N - L) s_L = A^(N - T) s_T, and T <= L + B - 1 <= N); N is a power of two, so A^N is what the squarings of the power
+// A^(N - T) leave in the base; one 12 x 12 Gauss-Jordan solve; then the chunk scan runs again from s* instead of from zero.
+// L == 1 gives N == 1, where rfft(b, 1) keeps b0 only: y = x prod b0, the zero-state step (s* = 0).
+template <bool PERIODIC>
+__global__ __launch_bounds__(EQ_NC) void k_eq_t(InView in, PostOp post, float *__restrict__ out, int64_t out_cand_stride,
+                                                 int C, int64_t L, const double *__restrict__ coef) {
     // the chunk states are only alive between the two passes, while the tile is not: one buffer for both
     constexpr size_t TILE_B = sizeof(float) * EQ_NC * (EQ_TS + 1), ZST_B = sizeof(double) * 12 * EQ_NC;
     __shared__ __attribute__((aligned(16))) char tz[TILE_B > ZST_B ? TILE_B : ZST_B];
@@ -204,6 +229,8 @@ __global__ __launch_bounds__(EQ_NC) void k_eq(InView in, PostOp post, float *__r
     int64_t len = L - start;
     len = len < 0 ? 0 : (len > B ? B : len);
     const int lr = tid >> 5, lj = tid & 31;
+    const int c_last = PERIODIC ? (int)((L - 1) / B) : 0;   // PERIODIC: the last chunk that holds samples walks on through zeros to its full length
+    const int64_t len_a = PERIODIC && tid == c_last ? B : len;
 
     double z[12];
     // tile staging: every thread fetches EQ_NC/8 = 32 scattered 4-byte pieces per tile; all of them
@@ -239,7 +266,7 @@ __global__ __launch_bounds__(EQ_NC) void k_eq(InView in, PostOp post, float *__r
         stage(t0);
         __syncthreads();
         if (t0 + EQ_TS < B) fetch(t0 + EQ_TS);
-        int64_t n = len - t0;
+        int64_t n = len_a - t0;
         n = n < 0 ? 0 : (n > EQ_TS ? EQ_TS : n);
         for (int j = 0; j < (int)n; ++j) (void)eq_step((double)tile[tid][j], sec, z);
     }
@@ -277,13 +304,95 @@ __global__ __launch_bounds__(EQ_NC) void k_eq(InView in, PostOp post, float *__r
             __syncthreads();
         }
     }
+    __shared__ double pvec[PERIODIC ? 24 : 1];        // s_T, then s*
+    __shared__ double gj[PERIODIC ? 12 * 13 : 1];     // [I - A^N | A^(N - T) s_T]
+    if constexpr (PERIODIC) {
+        if (tid < 64) {  // the chunk scan from zero, kept only as far as s_T
+            const int i = tid < 12 ? tid : 0;
+            double phi[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) phi[k] = mat[0][i * 12 + k];
+            double si = 0.0;
+            for (int c = 0; c <= c_last; ++c) {
+                double acc = zst[i][c];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) acc = fma(phi[k], __shfl(si, k), acc);
+                si = acc;
+            }
+            if (tid < 12) pvec[tid] = si;
+        }
+        if (tid < 12) {  // A again (the power above squared it away); mat[2] = I takes A^(N - T)
+            double e[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) e[k] = (k == tid) ? 1.0 : 0.0;
+            (void)eq_step(0.0, sec, e);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) mat[1][k * 12 + tid] = e[k];
+        }
+        if (tid < 144) mat[2][tid] = (tid / 12 == tid % 12) ? 1.0 : 0.0;
+        __syncthreads();
+        int kbits = 0;
+        while (((int64_t)1 << kbits) < 2 * L - 1) ++kbits;   // N = 2^kbits
+        const int64_t e1 = ((int64_t)1 << kbits) - (int64_t)(c_last + 1) * B;   // N - T >= 0
+        const int r = tid / 12, k = tid % 12;
+        for (int bit = 0; bit < kbits; ++bit) {
+            const bool take = (e1 >> bit) & 1;
+            double accr = 0.0, accb = 0.0;
+            if (tid < 144)
+                for (int m = 0; m < 12; ++m) {
+                    const double a = mat[1][r * 12 + m];
+                    if (take) accr = fma(a, mat[2][m * 12 + k], accr);
+                    accb = fma(a, mat[1][m * 12 + k], accb);
+                }
+            __syncthreads();
+            if (tid < 144) {
+                if (take) mat[2][tid] = accr;
+                mat[1][tid] = accb;
+            }
+            __syncthreads();
+        }
+        if (tid < 144) gj[r * 13 + k] = (r == k ? 1.0 : 0.0) - mat[1][tid];
+        if (tid < 12) {
+            double acc = 0.0;
+            for (int m = 0; m < 12; ++m) acc = fma(mat[2][tid * 12 + m], pvec[m], acc);
+            gj[tid * 13 + 12] = acc;
+        }
+        __syncthreads();
+        for (int p = 0; p < 12; ++p) {   // Gauss-Jordan with partial pivoting, one thread per element of the augmented matrix
+            int pr = p;
+            double best = fabs(gj[p * 13 + p]);
+            for (int q = p + 1; q < 12; ++q) {
+                const double v = fabs(gj[q * 13 + p]);
+                if (v > best) { best = v; pr = q; }
+            }
+            __syncthreads();
+            if (tid < 13 && pr != p) {
+                const double a = gj[p * 13 + tid], b = gj[pr * 13 + tid];
+                gj[p * 13 + tid] = b;
+                gj[pr * 13 + tid] = a;
+            }
+            __syncthreads();
+            const int gr = tid / 13, gc = tid % 13;
+            const bool act = tid < 12 * 13 && gr != p;
+            double f = 0.0, g = 0.0;
+            if (act) {
+                f = gj[gr * 13 + p] / gj[p * 13 + p];
+                g = gj[p * 13 + gc];
+            }
+            __syncthreads();
+            if (act) gj[gr * 13 + gc] = fma(-f, g, gj[gr * 13 + gc]);
+            __syncthreads();
+        }
+        if (tid < 12) pvec[12 + tid] = L == 1 ? 0.0 : gj[tid * 13 + 12] / gj[tid * 13 + tid];
+        __syncthreads();
+    }
     // ---- chunk scan: s_in[c+1] = Phi s_in[c] + z_c  (lanes 0..11 of wave 0, one row each) ------
     if (tid < 64) {
         const int i = tid < 12 ? tid : 0;
         double phi[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) phi[k] = mat[0][i * 12 + k];
-        double si = 0.0;
+        double si = PERIODIC ? pvec[12 + i] : 0.0;
         for (int c = 0; c < EQ_NC; ++c) {
             const double zc = zst[i][c];
             double acc = zc;
@@ -335,6 +444,9 @@ __global__ __launch_bounds__(EQ_NC) void k_eq(InView in, PostOp post, float *__r
     }
 }
 
+static constexpr auto k_eq = k_eq_t<false>;            // BasicParametricEQ, K-weighting: the causal recursion
+static constexpr auto k_eq_periodic = k_eq_t<true>;    // STITO_FX_DASP_EQ
+
 // The same cascade for other callers (features.hip: the K-weighting of BS.1770 = two biquads, the other four sections identity
 // rows b0 = 1): coef = n_cand rows of COEF_STRIDE doubles, out (n_cand, C, L) float32.
 int eq_cascade(const InView &in, float *out, int n_cand, int C, int64_t L, const double *coef, hipStream_t st) {
@@ -359,6 +471,7 @@ __global__ __launch_bounds__(256) void k_pointwise(InView in, float *__restrict_
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = x[i];
         if (KIND == STITO_FX_DISTORTION) y[i] = tanhf(v * g0) * g1;
+        else if (KIND == STITO_FX_DASP_DISTORTION) y[i] = tanhf(v * g0);  // dasp distortion(): tanh(x 10^(drive/20))
         else if (KIND == STITO_FX_GAIN) y[i] = v * g0;
         else y[i] = v;  // copy / up-mix
     }
@@ -792,7 +905,10 @@ __global__ __launch_bounds__(256) void k_normalize(float *__restrict__ a, int64_
 // ================================================================================================
 // host side
 // ================================================================================================
-static int fx_channels_after(const stito_fx_desc &fx, int c) { return (fx.num_channels == 2 && c == 1) ? 2 : c; }
+// (the dasp compressor sees the channels the signal has -- its side chain is their sum -- and never up-mixes)
+static int fx_channels_after(const stito_fx_desc &fx, int c) {
+    return (fx.num_channels == 2 && c == 1 && fx.kind != STITO_FX_DASP_COMPRESSOR) ? 2 : c;
+}
 
 static void reverb_geometry(double sr, ReverbGeom &g) {
     static const int comb_t[8] = {1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617};
@@ -871,6 +987,14 @@ static size_t reverb_split_bytes(const stito_fx_desc *chain, int n_fx, int64_t n
     return has && reverb_split(pop) ? align_up((size_t)pop * 2 * n_samples * sizeof(float), 256) : 0;
 }
 
+// dasp compressor: its look-ahead reads x[n - 512] while y[n] is written, so it cannot work in place; a stage that reads audio_dev
+// renders into this (pop, 2, L) scratch copy instead
+static size_t dasp_comp_bytes(const stito_fx_desc *chain, int n_fx, int64_t n_samples, int pop) {
+    bool has = false;
+    for (int i = 0; i < n_fx; ++i) has |= chain[i].kind == STITO_FX_DASP_COMPRESSOR;
+    return has ? align_up((size_t)pop * 2 * n_samples * sizeof(float), 256) : 0;
+}
+
 extern "C" size_t stito_render_workspace_bytes(const stito_fx_desc *chain, int n_fx, int in_channels,
                                                int64_t n_samples, int pop) {
     (void)in_channels;  // the compressor's share is sized for two channels per candidate whatever the chain does
@@ -879,7 +1003,7 @@ extern "C" size_t stito_render_workspace_bytes(const stito_fx_desc *chain, int n
     for (int i = 0; i < n_fx; ++i) has_comp |= chain[i].kind == STITO_FX_COMPRESSOR;
     size_t env = has_comp ? compressor_workspace_bytes(pop * 2, n_samples) : 0;  // block functions + boundary states
     return coef + env + conv_reverb_bytes(chain, n_fx, n_samples, pop) + reverb_split_bytes(chain, n_fx, n_samples, pop) +
-           align_up((size_t)pop * sizeof(float), 256) + 256;
+           dasp_comp_bytes(chain, n_fx, n_samples, pop) + align_up((size_t)pop * sizeof(float), 256) + 256;
 }
 
 static int peak_strided(const float *audio_dev, int pop, int64_t per, int64_t stride, float *peaks_dev, hipStream_t st) {
@@ -950,6 +1074,7 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
     char *crbuf = (char *)envbuf + (has_comp ? compressor_workspace_bytes(pop * 2, n_samples) : 0);
     float *rvbuf = (float *)(crbuf + conv_reverb_bytes(chain, n_fx, n_samples, pop));   // wet signals of the per-channel Freeverb
     const bool rv_split = reverb_split_bytes(chain, n_fx, n_samples, pop) > 0;
+    float *dcbuf = (float *)((char *)rvbuf + reverb_split_bytes(chain, n_fx, n_samples, pop));   // out-of-place copy of the dasp compressor
     // per-stage peaks (normalize_stages) live in the last pop floats of the workspace
     float *stage_peaks = (float *)(ws + (need - 256 - align_up((size_t)pop * sizeof(float), 256)));
 
@@ -973,6 +1098,7 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
     bool in_buffer = false, peaks_done = false;
     for (int i = 0; i < n_fx; ++i) {
         bool fused_next = false;  // stage i + 1 was absorbed by stage i's store
+        bool in_scratch = false;  // stage i left its output in dcbuf: the next stage reads it from there
         const stito_fx_desc &fx = chain[i];
         const int Cn = fx_channels_after(fx, C);
         const double *cf = coef + (int64_t)i * pop * COEF_STRIDE;
@@ -1006,6 +1132,26 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
                 if (rc) return rc;
                 break;
             }
+            case STITO_FX_DASP_EQ:
+                STITO_REQUIRE(L < ((int64_t)1 << 31) - 65536, STITO_E_UNSUPPORTED, "dasp parametric EQ: %lld samples per stream (k_eq_periodic indexes in 32 bits)", (long long)L);
+                hipLaunchKernelGGL(k_eq_periodic, dim3(S), dim3(EQ_NC), 0, st, in, PostOp{}, audio_dev, cand_stride, Cn, L, cf);
+                break;
+            case STITO_FX_DASP_COMPRESSOR: {
+                // From the shared input straight into audio_dev; from audio_dev into the scratch copy, which the next stage reads
+                // like any other input view -- or which is copied back where audio_dev itself is needed next (the end of the chain,
+                // a per-stage normalisation)
+                in_scratch = in_buffer;
+                const int rc = dasp_compressor_stage(in, in_scratch ? dcbuf : audio_dev, in_scratch ? (int64_t)Cn * L : cand_stride, pop, Cn, L, cf, st);
+                if (rc) return rc;
+                if (in_scratch && (i + 1 == n_fx || (fx.flags & STITO_FX_FLAG_NORMALIZE_AFTER))) {
+                    hipLaunchKernelGGL(k_pointwise<-1>, dim3(grid_x_for(L, S), S), dim3(256), 0, st, InView{dcbuf, (int64_t)Cn * L, L, Cn}, audio_dev, cand_stride, Cn, L, cf);
+                    in_scratch = false;
+                }
+                break;
+            }
+            case STITO_FX_DASP_DISTORTION:
+                hipLaunchKernelGGL(k_pointwise<STITO_FX_DASP_DISTORTION>, dim3(grid_x_for(L, S), S), dim3(256), 0, st, in, audio_dev, cand_stride, Cn, L, cf);
+                break;
             case STITO_FX_DISTORTION:
                 hipLaunchKernelGGL(k_pointwise<STITO_FX_DISTORTION>, dim3(grid_x_for(L, S), S), dim3(256), 0, st, in, audio_dev, cand_stride, Cn, L, cf);
                 break;
@@ -1057,8 +1203,8 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
         }
         STITO_LAUNCH_CHECK();
         C = Cn;
-        in = InView{audio_dev, cand_stride, L, C};
-        in_buffer = true;
+        in = in_scratch ? InView{dcbuf, (int64_t)C * L, L, C} : InView{audio_dev, cand_stride, L, C};
+        in_buffer = !in_scratch;
         if (fused_next) ++i;
         if (fx.flags & STITO_FX_FLAG_NORMALIZE_AFTER) {  // normalize_stages (style_transfer.py:106-107)
             int rc = peak_strided(audio_dev, pop, (int64_t)C * L, cand_stride, stage_peaks, st);

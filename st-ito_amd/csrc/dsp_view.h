@@ -38,4 +38,9 @@ size_t compressor_workspace_bytes(int n_streams, int64_t n_samples);
 int compressor_stage(const InView &in, float *audio_dev, int64_t cand_stride, int pop, int C, int64_t n_samples,
                      const double *coef, void *workspace, hipStream_t st);
 
+// dasp compressor stage with its 512-sample look-ahead (modfx.hip): one gain per candidate from the sum of its C channels; NOT in
+// place: out (pop candidates, out_cand_stride floats apart, C channels of n_samples) must not overlap the input view.
+int dasp_compressor_stage(const InView &in, float *out, int64_t out_cand_stride, int pop, int C, int64_t n_samples, const double *coef,
+                          hipStream_t st);
+
 }  // namespace stito

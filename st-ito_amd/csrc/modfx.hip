@@ -153,6 +153,124 @@ __global__ __launch_bounds__(256) void k_dasp_compressor(const float *__restrict
     }
 }
 
+// ---- the same compressor as a chain stage (STITO_FX_DASP_COMPRESSOR: apply_compressor, effects.py:623-648) -------------------
+// One parameter set per candidate (coefficient row: threshold, ratio, alpha_A, knee, make-up, float32 values), lookahead_samples =
+// 512: y[n] = x[n - 512] g[n] with zeros in front, the gain undelayed -- so the stage is not in place.  One workgroup per candidate
+// (one gain for all of its channels), 256 time chunks; global memory is touched in 16-sample rows through LDS tiles (a thread's
+// own chunk would be a stride of B floats between lanes).  The smoother is the library's frequency-sampled one-pole, i.e. circular
+// over N = 2^ceil(log2(2 L - 1)): the recursion started from g* = a^(N - L) g_L / (1 - a^N), g_L its zero-state value after the L
+// samples; at a 250 ms attack and 4 096 samples a^N is 0.22.  L <= 512: the delayed signal is all zeros.
+static constexpr int DC_NC = 256;              // time chunks per candidate == threads per workgroup
+static constexpr int DC_TS = 16;               // samples per LDS tile row
+static constexpr int DC_NG = DC_NC / DC_TS;    // 16-lane groups: a group stages one row at a time
+static constexpr int DC_LOOK = 512;
+
+__global__ __launch_bounds__(DC_NC) void k_dasp_comp_stage(InView in, float *__restrict__ out, int64_t out_cand_stride, int C, int64_t L,
+                                                            const double *__restrict__ coef) {
+    __shared__ float side[DC_NC][DC_TS + 1];
+    __shared__ float dly[2][DC_NC][DC_TS + 1];
+    __shared__ double ends[DC_NC], starts[DC_NC];
+    const int cand = blockIdx.x, tid = threadIdx.x;
+    const double *cf = coef + (int64_t)cand * COEF_STRIDE;
+    const float thr = (float)cf[0], ratio = (float)cf[1], alpha_f = (float)cf[2], knee = (float)cf[3], makeup = (float)cf[4];
+    const double a = (double)alpha_f, b = (double)(1.0f - alpha_f);
+    const float *x0 = in_ptr(in, cand, 0), *x1 = in_ptr(in, cand, C - 1);
+    float *y = out + (int64_t)cand * out_cand_stride;
+    if (L <= DC_LOOK) {
+        for (int64_t i = tid; i < (int64_t)C * L; i += DC_NC) y[i] = 0.0f;
+        return;
+    }
+    const int64_t B = (L + DC_NC - 1) / DC_NC, s0 = (int64_t)tid * B;
+    int64_t len = L - s0;
+    len = len < 0 ? 0 : (len > B ? B : len);
+    const int lr = tid / DC_TS, lj = tid % DC_TS;
+    // row `it` of this thread's group: chunk it * DC_NG + lr, sample t0 + lj of it
+    auto pos = [&](int it, int64_t t0) { return (int64_t)(it * DC_NG + lr) * B + t0 + lj; };
+    auto stage_side = [&](int64_t t0) {
+        const bool in_chunk = t0 + lj < B;
+#pragma unroll
+        for (int it = 0; it < DC_TS; ++it) {
+            const int64_t p = pos(it, t0);
+            float v = 0.0f;
+            if (in_chunk && p < L) v = C == 2 ? x0[p] + x1[p] : x0[p];
+            side[it * DC_NG + lr][lj] = v;
+        }
+    };
+    // ---- pass A: zero-state value of the smoother at the end of every chunk ----
+    double g = 0.0;
+    for (int64_t t0 = 0; t0 < B; t0 += DC_TS) {
+        __syncthreads();
+        stage_side(t0);
+        __syncthreads();
+        int64_t n = len - t0;
+        n = n < 0 ? 0 : (n > DC_TS ? DC_TS : n);
+        for (int j = 0; j < (int)n; ++j) g = fma(a, g, b * (double)dasp_gain_computer(side[tid][j], thr, ratio, knee, 1e-8f));
+    }
+    ends[tid] = g;
+    __syncthreads();
+    if (tid == 0) {
+        const double aB = pow(a, (double)B);
+        const int c_last = (int)((L - 1) / B);
+        double s = 0.0;
+        for (int c = 0; c < c_last; ++c) s = fma(aB, s, ends[c]);
+        const double gL = fma(pow(a, (double)(L - (int64_t)c_last * B)), s, ends[c_last]);
+        int kbits = 0;
+        while (((int64_t)1 << kbits) < 2 * L - 1) ++kbits;
+        const double N = (double)((int64_t)1 << kbits);
+        s = pow(a, N - (double)L) * gL / (1.0 - pow(a, N));   // g*
+        for (int c = 0; c < DC_NC; ++c) {   // (every chunk but the last that holds samples has length B; later starts are never used)
+            starts[c] = s;
+            s = fma(aB, s, ends[c]);
+        }
+    }
+    __syncthreads();
+    // ---- pass B: the smoother from its true start, gain, delayed signal ----
+    g = starts[tid];
+    for (int64_t t0 = 0; t0 < B; t0 += DC_TS) {
+        __syncthreads();
+        stage_side(t0);
+        {
+            const bool in_chunk = t0 + lj < B;
+#pragma unroll
+            for (int it = 0; it < DC_TS; ++it) {
+                const int64_t p = pos(it, t0), q = p - DC_LOOK;
+                const bool ok = in_chunk && p < L && q >= 0;
+                dly[0][it * DC_NG + lr][lj] = ok ? x0[q] : 0.0f;
+                if (C == 2) dly[1][it * DC_NG + lr][lj] = ok ? x1[q] : 0.0f;
+            }
+        }
+        __syncthreads();
+        int64_t n = len - t0;
+        n = n < 0 ? 0 : (n > DC_TS ? DC_TS : n);
+        for (int j = 0; j < (int)n; ++j) {
+            g = fma(a, g, b * (double)dasp_gain_computer(side[tid][j], thr, ratio, knee, 1e-8f));
+            const float lin = powf(10.0f, ((float)g + makeup) / 20.0f);
+            dly[0][tid][j] *= lin;
+            if (C == 2) dly[1][tid][j] *= lin;
+        }
+        __syncthreads();
+        {
+            const bool in_chunk = t0 + lj < B;
+#pragma unroll
+            for (int it = 0; it < DC_TS; ++it) {
+                const int64_t p = pos(it, t0);
+                if (in_chunk && p < L) {
+                    y[p] = dly[0][it * DC_NG + lr][lj];
+                    if (C == 2) y[L + p] = dly[1][it * DC_NG + lr][lj];
+                }
+            }
+        }
+    }
+}
+
+int dasp_compressor_stage(const InView &in, float *out, int64_t out_cand_stride, int pop, int C, int64_t L, const double *coef,
+                          hipStream_t st) {
+    STITO_REQUIRE(C == 1 || C == 2, STITO_E_INVALID, "dasp compressor: %d channels", C);
+    hipLaunchKernelGGL(k_dasp_comp_stage, dim3((unsigned)pop), dim3(DC_NC), 0, st, in, out, out_cand_stride, C, L, coef);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
 }  // namespace stito
 
 using namespace stito;

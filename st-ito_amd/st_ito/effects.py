@@ -241,6 +241,51 @@ def chorus_lfo_device(sample_rate: float, n_samples: int, device):
     return t
 
 
+# ---- the reference's differentiable family (effects.py:545-780, on dasp-pytorch) as forward-only chain stages ---------------
+class DaspParametricEQ(_BasicEffect):
+    """apply_parametric_eq (reference effects.py:651-706 -> dasp_pytorch.parametric_eq): low shelf, four peaking sections, high
+    shelf, applied by frequency sampling (circular over the FFT length; restated from the library's published algorithm, parity
+    unpinned).  Parameter order and ranges are the denormalize() calls of the reference."""
+
+    KIND = _hip.FX_DASP_EQ
+
+    def __init__(self):
+        sections = ["low_shelf", "band0", "band1", "band2", "band3", "high_shelf"]
+        self.parameters = OrderedDict()
+        for sec, f0 in zip(sections, (80.0, 300.0, 1000.0, 3000.0, 10000.0, 12000.0)):
+            fname = "cutoff_freq" if sec.endswith("shelf") else "center_freq"
+            self.parameters[f"{sec}_gain_db"] = Parameter(0.0, -18.0, 18.0)
+            self.parameters[f"{sec}_{fname}"] = Parameter(f0, 20.0, 20000.0)
+            self.parameters[f"{sec}_q_factor"] = Parameter(0.707, 0.1, 10.0)
+
+
+class DaspCompressor(_BasicEffect):
+    """apply_compressor (reference effects.py:623-648 -> dasp_pytorch.compressor, lookahead_samples=512).  The side chain is the
+    sum of the channels the audio has; release_ms is declared and, as in the library, unused."""
+
+    KIND = _hip.FX_DASP_COMPRESSOR
+
+    def __init__(self, threshold_db: float = 0.0, ratio: float = 4.0, attack_ms: float = 10.0, release_ms: float = 100.0,
+                 knee_db: float = 6.0, makeup_gain_db: float = 0.0):
+        self.parameters = OrderedDict([
+            ("threshold_db", Parameter(threshold_db, -60.0, 0.0)),
+            ("ratio", Parameter(ratio, 1.0, 20.0)),
+            ("attack_ms", Parameter(attack_ms, 0.1, 250.0)),
+            ("release_ms", Parameter(release_ms, 10.0, 2000.0)),
+            ("knee_db", Parameter(knee_db, 1.0, 24.0)),
+            ("makeup_gain_db", Parameter(makeup_gain_db, 0.0, 24.0)),
+        ])
+
+
+class DaspDistortion(_BasicEffect):
+    """apply_distortion (reference effects.py:545-555 -> dasp_pytorch.distortion): tanh(x * 10^(drive_db / 20))."""
+
+    KIND = _hip.FX_DASP_DISTORTION
+
+    def __init__(self, drive_db: float = 0.0):
+        self.parameters = OrderedDict([("drive_db", Parameter(drive_db, 0.0, 48.0))])
+
+
 BASIC_CHAINS = {
     # scripts/run_optim.py:375-407 (--effect-type basic)
     "basic": [("ParametricEQ", BasicParametricEQ, 1), ("Compressor", BasicCompressor, 1),
@@ -255,6 +300,9 @@ BASIC_CHAINS = {
     # functools.partial(NoiseShapedReverb, num_samples=96000) for the 2 s impulse response)
     "eq-convreverb-gain": [("ParametricEQ", BasicParametricEQ, 1), ("ConvReverb", NoiseShapedReverb, 2),
                            ("Gain", BasicGain, 1)],
+    # apply_complex_autodiff_processor (effects.py:729-780): the processor behind `run_optim.py --algorithm autodiff`, D = 51
+    "autodiff": [("ParametricEQ", DaspParametricEQ, 1), ("Compressor", DaspCompressor, 1), ("Distortion", DaspDistortion, 1),
+                 ("Reverb", NoiseShapedReverb, 2), ("Gain", BasicGain, 1)],
 }
 
 
@@ -271,3 +319,80 @@ def make_plugins(chain="basic", with_bypass: bool = False):
         plugins[name] = {"class_path": cls, "num_params": len(names), "num_channels": nch,
                          "fixed_parameters": {}, "instance": inst, "parameter_names": names}
     return plugins
+
+
+# ---- the reference's apply_* call surface (effects.py:532-780), forward only -------------------------------------------------
+_APPLY_PLUGINS = OrderedDict()   # (stage names, sample rate, seed, device) -> plugins, least recently used first
+_APPLY_PLUGINS_MAX = 8           # a reverb entry pins its filtered noise bank on its device, so the cache is bounded
+
+
+def _apply(spec, audio, params, sample_rate, seed: int = 0):
+    """audio (bs, chs, n), params (bs, num_params) raw values in [0, 1] -> (bs, chs', n) float32 on the GPU: item b through the
+    chain `spec` with parameters params[b] -- one stito_render_population_multi call with as many inputs as candidates."""
+    import functools
+
+    import torch
+
+    from .engine import _current_device, render_population
+
+    dev = _current_device()
+    bs, chs, seq_len = audio.shape
+    bs_p, num_params = params.shape
+    assert bs_p == bs, "audio and params must have the same batch size"
+    key = (tuple(name for name, _, _ in spec), float(sample_rate), int(seed), str(dev))
+    plugins = _APPLY_PLUGINS.get(key)
+    if plugins is None:  # (the reverb's noise bank is filtered once per sample rate, seed and device)
+        spec = [(name, functools.partial(cls, sample_rate=sample_rate, seed=seed) if cls is NoiseShapedReverb else cls, nch)
+                for name, cls, nch in spec]
+        plugins = _APPLY_PLUGINS[key] = make_plugins(spec)
+        while len(_APPLY_PLUGINS) > _APPLY_PLUGINS_MAX:
+            _APPLY_PLUGINS.popitem(last=False)
+    else:
+        _APPLY_PLUGINS.move_to_end(key)
+    x = audio.detach().to(dev, torch.float32).contiguous()
+    w = params.detach().to(dev, torch.float64).contiguous()
+    return render_population(plugins, x, w, sample_rate)[0]
+
+
+def apply_gain(audio, params, sample_rate: int):
+    """reference effects.py:532-542: gain -48 .. 48 dB."""
+    assert params.shape[1] == 1, "Number of parameters must be 1"
+    return _apply([("Gain", BasicGain, 1)], audio, params, sample_rate)
+
+
+def apply_distortion(audio, params, sample_rate: int):
+    """reference effects.py:545-555: drive 0 .. 48 dB."""
+    assert params.shape[1] == 1, "Number of parameters must be 1"
+    return _apply([("Distortion", DaspDistortion, 1)], audio, params, sample_rate)
+
+
+def apply_reverb(audio, params, sample_rate: int, seed: int = 0):
+    """reference effects.py:558-620.  The library draws its noise afresh on every call; here it is the seeded bank of
+    make_noise_bank, and `seed` (an extension) selects it."""
+    assert params.shape[1] == 25, "Number of parameters must be 25"
+    return _apply([("Reverb", NoiseShapedReverb, 2)], audio, params, sample_rate, seed)
+
+
+def apply_compressor(audio, params, sample_rate: int):
+    """reference effects.py:623-648."""
+    assert params.shape[1] == 6, "Number of parameters must be 6"
+    return _apply([("Compressor", DaspCompressor, 1)], audio, params, sample_rate)
+
+
+def apply_parametric_eq(audio, params, sample_rate: int):
+    """reference effects.py:651-706."""
+    assert sample_rate >= 44100, "Sample rate must be at least 44100 Hz"
+    assert params.shape[1] == 18, "Number of parameters must be 18"
+    return _apply([("ParametricEQ", DaspParametricEQ, 1)], audio, params, sample_rate)
+
+
+def apply_complex_autodiff_processor(audio, params, sample_rate: int, *args, seed: int = 0):
+    """reference effects.py:729-780: EQ -> compressor -> distortion -> reverb -> gain, 18 + 6 + 1 + 25 + 1 = 51 parameters, as one
+    render of the "autodiff" chain.  (apply_simple_autodiff_processor is left out: in the reference it hands 15 parameters to
+    apply_parametric_eq, which asserts 18, so it cannot run there either.)"""
+    import torch
+
+    assert params.shape[1] == 18 + 6 + 1 + 25 + 1
+    assert sample_rate >= 44100, "Sample rate must be at least 44100 Hz"
+    assert torch.all(params >= 0) and torch.all(params <= 1)
+    return _apply(BASIC_CHAINS["autodiff"], audio, params, sample_rate, seed)
