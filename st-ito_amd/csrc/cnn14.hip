@@ -1244,17 +1244,30 @@ static void cnn14_dims(int64_t T, int M, int H[7], int W[7]) {
     H[6] = H[5]; W[6] = W[5];
 }
 
+// conv i of the trunk on S streams: a block's first conv takes the block's input channels, its second pools (not in conv_block6)
+struct Cnn14Layer {
+    ConvShape c;
+    int pool;
+    size_t out_floats;   // of its output map, per stream
+    bool supported(int algo) const { return stito_conv3x3_supported(c.S, c.H, c.W, c.Cin, c.Cout, pool, algo) != 0; }
+    size_t workspace_bytes(int algo) const { return stito_conv3x3_workspace_bytes(c.S, c.H, c.W, c.Cin, c.Cout, pool, algo); }
+};
+
+static Cnn14Layer cnn14_layer(const stito_cnn14_weights *w, const int H[7], const int W[7], int i, int S) {
+    const int blk = i / 2, j = i % 2, cout = w->channels[blk + 1], pool = (j == 1 && blk < 5) ? 1 : 0;
+    return Cnn14Layer{ConvShape{S, H[blk], W[blk], j == 0 ? w->channels[blk] : cout, cout}, pool, (size_t)H[blk + pool] * W[blk + pool] * cout};
+}
+
 // the conv workspace: the largest need among the layers whose algorithm needs one (and conv_block1 in one launch)
 static size_t cnn14_pre_bytes(const stito_cnn14_weights *w, int n_streams, const int H[7], const int W[7]) {
     size_t v = 0;
     for (int i = 0; i < STITO_CNN14_NUM_CONVS; ++i) {
         const int algo = w->conv_wino_algo[i];
         if (w->conv_wino_dev[i] == nullptr || !conv_algo(algo).needs_workspace()) continue;
-        const int blk = i / 2, j = i % 2;
-        const int ci = j == 0 ? w->channels[blk] : w->channels[blk + 1], pool = (j == 1 && blk < 5) ? 1 : 0;
-        size_t need = stito_conv3x3_workspace_bytes(n_streams, H[blk], W[blk], ci, w->channels[blk + 1], pool, algo);
+        const Cnn14Layer l = cnn14_layer(w, H, W, i, n_streams);
+        size_t need = l.workspace_bytes(algo);
         if (w->conv_alt_dev[i] != nullptr) {
-            const size_t alt = stito_conv3x3_workspace_bytes(n_streams, H[blk], W[blk], ci, w->channels[blk + 1], pool, w->conv_alt_algo[i]);
+            const size_t alt = l.workspace_bytes(w->conv_alt_algo[i]);
             need = alt > need ? alt : need;
         }
         v = need > v ? need : v;
@@ -1278,8 +1291,7 @@ struct ChunkPlan {
 };
 
 static size_t conv_out_floats_per_stream(const stito_cnn14_weights *w, const int H[7], const int W[7], int i) {
-    const int blk = i / 2, j = i % 2;
-    return (j == 1 && blk < 5) ? (size_t)H[blk + 1] * W[blk + 1] * w->channels[blk + 1] : (size_t)H[blk] * W[blk] * w->channels[blk + 1];
+    return cnn14_layer(w, H, W, i, 1).out_floats;
 }
 
 static ChunkPlan cnn14_chunk_plan(const stito_cnn14_weights *w, int n_streams, const int H[7], const int W[7], bool fuse1r) {
@@ -1427,11 +1439,8 @@ struct Trunk {
     // does conv i + 1 run a kernel that scales its transformed input by per-stream maxima of conv i's output?
     bool next_wants_amax(int i, int S) const {
         if (i + 1 >= STITO_CNN14_NUM_CONVS) return false;
-        const int nb = (i + 1) / 2, nj = (i + 1) % 2;
-        const int nci = nj == 0 ? w->channels[nb] : w->channels[nb + 1], npool = (nj == 1 && nb < 5) ? 1 : 0;
         const int nalgo = w->conv_wino_algo[i + 1];
-        return w->conv_wino_dev[i + 1] != nullptr && conv_algo(nalgo).reads_amax &&
-               stito_conv3x3_supported(S, H[nb], W[nb], nci, w->channels[nb + 1], npool, nalgo);
+        return w->conv_wino_dev[i + 1] != nullptr && conv_algo(nalgo).reads_amax && cnn14_layer(w, H, W, i + 1, S).supported(nalgo);
     }
 
     // conv_block1 as one launch on the register-resident F(2x2,3x3) kernel (it computes the first conv into its patch ring)
@@ -1450,30 +1459,27 @@ struct Trunk {
     // conv i on streams s0 .. s0 + S - 1: in / out point at the first of them; have_amax: in -- the producer of `in` reported
     // these streams' maxima (buffer of conv i - 1), out -- this launch reported its own
     int conv(int i, const float *in, float *out, int S, int s0, bool &have_amax) const {
-        const int blk = i / 2, j = i % 2;
-        const int cin = w->channels[blk], cout = w->channels[blk + 1];
-        const int ci = j == 0 ? cin : cout, pool = (j == 1 && blk < 5) ? 1 : 0;
+        const Cnn14Layer l = cnn14_layer(w, H, W, i, S);
         // Winograd where a transformed weight set was supplied and the map fits; direct otherwise.  An id that names no Winograd
         // packing means the F(2x2,3x3) one.  (a split packing has no float32 fallback: the direct kernel takes over)
         int walgo = conv_algo(w->conv_wino_algo[i]).winograd ? w->conv_wino_algo[i] : STITO_CONV_WINOGRAD;
         const int same = conv_algo(walgo).same_packing;
-        if (same >= 0 && !stito_conv3x3_supported(S, H[blk], W[blk], ci, cout, pool, walgo)) walgo = same;
+        if (same >= 0 && !l.supported(walgo)) walgo = same;
         const float *wino_w = w->conv_wino_dev[i];
         if (walgo == STITO_CONV_WINOGRAD_F4_SPLIT3 && w->conv_alt_dev[i] != nullptr && w->conv_alt_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT2 &&
-            4 * wino43_split3_workgroups(ConvShape{S, H[blk], W[blk], ci, cout}, pool != 0) < 3 * n_cus &&
-            stito_conv3x3_supported(S, H[blk], W[blk], ci, cout, pool, STITO_CONV_WINOGRAD_F4_SPLIT2)) {
+            4 * wino43_split3_workgroups(l.c, l.pool != 0) < 3 * n_cus && l.supported(STITO_CONV_WINOGRAD_F4_SPLIT2)) {
             walgo = STITO_CONV_WINOGRAD_F4_SPLIT2;   // too few of the large workgroups for this batch: the alternative packing
             wino_w = w->conv_alt_dev[i];
         }
-        const bool wino = wino_w != nullptr && stito_conv3x3_supported(S, H[blk], W[blk], ci, cout, pool, walgo);
-        TimedLaunch t((hipStream_t)stream, g_conv_timing.on && ci % 8 == 0);
+        const bool wino = wino_w != nullptr && l.supported(walgo);
+        TimedLaunch t((hipStream_t)stream, g_conv_timing.on && l.c.Cin % 8 == 0);
         STITO_TRY(t.begin(i));
         const int algo_i = wino ? walgo : STITO_CONV_DIRECT;
         // can this layer's kernel report the maxima the next one wants?  (the first conv's own kernel can)
         unsigned *amax_out = nullptr;
-        if ((conv_algo(algo_i).reports_amax || (ci == 1 && !pool)) && next_wants_amax(i, S)) amax_out = amax_of(i, s0);
-        const int rc = conv3x3_ws(algo_i, ConvArgs{in, wino ? wino_w : w->conv_w_dev[i], w->bn_scale_dev[i], w->bn_shift_dev[i], out,
-                                                   ConvShape{S, H[blk], W[blk], ci, cout}, pool != 0, vbuf, vbytes, (hipStream_t)stream,
+        if ((conv_algo(algo_i).reports_amax || (l.c.Cin == 1 && !l.pool)) && next_wants_amax(i, S)) amax_out = amax_of(i, s0);
+        const int rc = conv3x3_ws(algo_i, ConvArgs{in, wino ? wino_w : w->conv_w_dev[i], w->bn_scale_dev[i], w->bn_shift_dev[i], out, l.c,
+                                                   l.pool != 0, vbuf, vbytes, (hipStream_t)stream,
                                                    (have_amax && i > 0) ? amax_of(i - 1, s0) : nullptr, amax_out, g_wino_trace});
         if (rc) return rc;
         have_amax = amax_out != nullptr;

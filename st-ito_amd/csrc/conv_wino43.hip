@@ -886,6 +886,8 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s(const char *__rest
 //     (agent-scope release / acquire) just before it reads them.  Same loads, same products, same additions in the same order:
 //     IDENTICAL BITS (tested), twice the workgroups.  Sweep-0 workgroups have the lower indices, are dispatched first and wait for
 //     nobody, so the wait cannot deadlock however many workgroups are resident.
+// f32x4 of partial outputs per workgroup item, [tile half][r * 4 + c][thread]: the stride of my_partial below (256 KB)
+static constexpr int S43B_PARTIAL = 2 * 16 * W43_THREADS;
 template <int TTW, bool POOL, bool SWSPLIT>
 __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s2(const char *__restrict__ vsl, const char *__restrict__ usl,
                                                                 const float *__restrict__ scale, const float *__restrict__ shift,
@@ -1124,6 +1126,8 @@ __device__ __forceinline__ const char *w43_uniform(const char *p) {
 // their Z in the scratch area as before and count themselves in (agent-scope release), the row-5 workgroup waits for the count of five
 // before it reads them back.  Same products, same additions, same order: identical bits; six times the workgroups for a batch that
 // would leave most CUs idle.  Rows 0 .. 4 have the lower workgroup indices and wait for nobody: no deadlock whatever is resident.
+// f32x4 of partial outputs per workgroup item, [wave][blk][quad][row 0..4][c][lane]: the stride of my_partial below (1.25 MB)
+static constexpr int S43C_PARTIAL = 8 * 2 * 4 * 20 * 64;
 template <int TTW, bool POOL, bool SWSPLIT>
 __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__restrict__ vsl, const char *__restrict__ usl,
                                                                 const float *__restrict__ scale, const float *__restrict__ shift,
@@ -1526,9 +1530,11 @@ static int w43_staging(const ConvShape &c, bool pool, Wino43Geom &g, size_t &lds
     return STITO_OK;
 }
 
+// channels and maps every kernel of this file takes (before its geometry is asked for: that divides by Cout / 64)
+static bool w43_map_ok(const ConvShape &c, bool pool) { return c.Cin % 8 == 0 && c.Cout % 64 == 0 && !(pool && (c.H < 2 || c.W < 2)); }
+
 static bool wino43_supported(const ConvShape &c, bool pool) {
-    if (c.Cin % 8 != 0 || c.Cout % 64 != 0) return false;
-    if (pool && (c.H < 2 || c.W < 2)) return false;
+    if (!w43_map_ok(c, pool)) return false;
     Wino43Geom g;
     size_t lds;
     int64_t blocks;
@@ -1700,142 +1706,217 @@ static int w43_stream_amax(const ConvArgs &a, unsigned *amax_ws, const unsigned 
     return STITO_OK;
 }
 
-// The launch of a workspace algorithm of this file: the shapes it covers, the workspace it needs, then launch(TTW, POOL)
+// ---- the workspace algorithms: hoisted input transform, split precision, two sweeps, six sweeps ----
+enum W43Kind { W43_PRE, W43_SPLIT, W43_SPLIT2, W43_SPLIT3 };
+
+// One launch of one of them, worked out once from (shape, pool): `supported`, `workspace_bytes`, `issued_flops`,
+// wino43_split3_workgroups and the launcher all read this, and the launcher's pointers are ws + region.off -- a region's size is
+// spelled in w43_plan and nowhere else.
+struct W43Plan {
+    struct Region { size_t off, bytes; };
+    bool ok = false;         // the algorithm covers the shape
+    Wino43Geom g;            // of the shape, as the transform pass takes it; the conv kernel's adds the four below (w43_conv_geom)
+    int64_t items = 0;       // what a workgroup takes: a pixel block (hoisted, split), a pair (two sweeps) or a quad (six sweeps) of them
+    int64_t v_blocks = 0;    // pixel blocks the transform pass writes: whole items (blocks past the map transform to zeros)
+    int ct_group = 0;        // channel tiles side by side on an XCD
+    int xcd_m = 0;           // two and six sweeps: the XCDs as xcd_m item classes x 8 / xcd_m channel-tile ranges
+    int64_t grid = 0;        // workgroups, whole XCD rounds (a launch with the sweeps split: one such grid per sweep); 0: none
+    Region v{}, amax{}, partial{}, flags{};   // V slabs | stream maxima | partial outputs per item | hand-off flags or counts per item
+    size_t total = 0;        // workspace bytes; 0: not covered, or no grid a launch can take
+    void add(Region &r, size_t bytes) { r = Region{total, bytes}; total += align_up(bytes, 256); }
+};
+
+// whole XCD rounds: 8 XCDs x (groups of 32 / ct_group of an XCD's items) x (groups of ct_group channel tiles) x 32 workgroups
+static int64_t w43_xcd_round_grid(int64_t items_per_xcd, int n_tiles, int ct_group) {
+    const int bm = 32 / ct_group;
+    return 8 * ((items_per_xcd + bm - 1) / bm) * (n_tiles / ct_group) * 32;
+}
+
+// tuning aid (tools/conv_bench.py): ct_group from the environment, where that is a power of two up to 32 that divides the tile count
+static int w43_ct_group_env(const char *var, int n_tiles, int ct_group) {
+    const char *e = getenv(var);
+    const int ae = e ? atoi(e) : 0;
+    return ae >= 1 && ae <= 32 && (ae & (ae - 1)) == 0 && n_tiles % ae == 0 ? ae : ct_group;
+}
+
+// (the environment is read on every call: the tests flip it between launches)
+static W43Plan w43_plan(W43Kind k, const ConvShape &c, bool pool) {
+    W43Plan p;
+    const bool sweeps = k == W43_SPLIT2 || k == W43_SPLIT3;
+    // channel tiles the workgroup order deals in fours / eights (six sweeps: 128-cout tiles); split operands: 64 input channels per slab pair
+    if (k == W43_SPLIT3 ? c.Cout % 512 != 0 : (c.Cout % 256 != 0 || (c.Cout >= 1024 && c.Cout % 512 != 0))) return p;
+    if (k != W43_PRE && (c.Cin % 64 != 0 || ((int64_t)c.Cin * c.H * c.W) % 8 != 0)) return p;
+    size_t lds;
+    int64_t blocks;
+    if (!w43_map_ok(c, pool) || !w43_geometry_any(c, pool, p.g, lds, blocks)) return p;
+    p.ok = true;
+    const int per_item = k == W43_SPLIT3 ? 4 : (k == W43_SPLIT2 ? 2 : 1);
+    p.items = (blocks / (c.Cout / 64) + per_item - 1) / per_item;
+    p.v_blocks = p.items * per_item;
+    int n_tiles = c.Cout / (k == W43_SPLIT3 ? 128 : 64), xm = 8;
+    if (sweeps) {
+        // XCD split (see the kernels): the xm in {8, 4, 2, 1} (six sweeps: not 1) with the fewest slab streams per L2,
+        // items / xm + tiles / (8 / xm); 8 on a tie
+        const int xm_min = k == W43_SPLIT3 ? 2 : 1;
+        for (int cand = 4; cand >= xm_min; cand >>= 1)
+            if (n_tiles % (8 / cand) == 0 && (p.items + cand - 1) / cand + n_tiles / (8 / cand) < (p.items + xm - 1) / xm + n_tiles / (8 / xm)) xm = cand;
+        if (const char *e = getenv(k == W43_SPLIT3 ? "STITO_W43S3_XM" : "STITO_W43S2_XM")) {   // tuning aid
+            const int xe = atoi(e);
+            if (xe >= xm_min && xe <= 8 && (xe & (xe - 1)) == 0 && n_tiles % (8 / xe) == 0) xm = xe;
+        }
+        p.xcd_m = xm;
+        n_tiles /= 8 / xm;
+    }
+    const int64_t per_xcd = (p.items + xm - 1) / xm;
+    int ag;
+    switch (k) {
+        case W43_PRE:
+            // swept 1..32 at 512 streams (tools/conv_bench.py --modes 9): 4 is best for 8 tiles (conv_block4: 3.17 / 5.69 ms against
+            // 3.63 / 6.59 for 1), 8 from 16 tiles up (1-4 % over 4), 32 loses 15 % at 32 tiles
+            ag = n_tiles >= 16 ? 8 : 4;
+            break;
+        case W43_SPLIT:   // swept again with the round's final kernels (profiles/round3_stream_loop_experiments.txt, 15.)
+            ag = w43_ct_group_env("STITO_W43S_CTG", n_tiles, n_tiles >= 16 ? 8 : (n_tiles >= 8 ? 4 : 2));
+            break;
+        default:
+            // a power of two that divides the tile count (cout 1536 has 12 tiles of 128, 6 per XCD half: ADVICE r5); six sweeps: from 4,
+            // grown while a round of 32 workgroups is not full
+            ag = k == W43_SPLIT3 ? 4 : 8;
+            while (ag > 1 && n_tiles % ag != 0) ag >>= 1;
+            while (k == W43_SPLIT3 && ag < n_tiles && ag < 32 && 32 / ag > per_xcd && n_tiles % (2 * ag) == 0) ag *= 2;
+            ag = w43_ct_group_env(k == W43_SPLIT3 ? "STITO_W43S3_CTG" : "STITO_W43S_CTG", n_tiles, ag);
+    }
+    p.ct_group = ag;
+    p.grid = n_tiles % ag == 0 ? w43_xcd_round_grid(per_xcd, n_tiles, ag) : 0;
+    if (sweeps && !(p.grid > 0 && p.grid < (1ll << 31))) {
+        p.ok = k == W43_SPLIT2;   // six sweeps: "supported" means the launcher finds a grid for it
+        return p;
+    }
+    // a pixel block's V slabs: 36 positions x 32 tiles x 4 bytes per input channel (an f32, or the hi and lo f16 of a split operand)
+    p.add(p.v, (size_t)p.v_blocks * c.Cin * (36 * 32 * sizeof(float)));
+    if (k != W43_PRE) p.add(p.amax, (size_t)c.S * sizeof(unsigned));
+    if (sweeps) {
+        p.add(p.partial, (size_t)p.grid * (k == W43_SPLIT3 ? S43C_PARTIAL : S43B_PARTIAL) * sizeof(f32x4));
+        p.add(p.flags, (size_t)p.grid * sizeof(unsigned));   // read and zeroed only when the sweeps are split
+    }
+    return p;
+}
+
+template <W43Kind K>
+static bool w43_supported(const ConvShape &c, bool pool) { return w43_plan(K, c, pool).ok; }
+
+template <W43Kind K>
+static size_t w43_workspace_bytes(const ConvShape &c, bool pool) { return w43_plan(K, c, pool).total; }
+
+// f16-pipe FLOPs the two- / six-sweep kernel issues: items (padded pixel blocks included) x channel tiles x T x T x 36 x cin x 3 products
+// with its T = 64 / 128 pixels and couts per tile
+template <W43Kind K>
+static double w43_sweeps_issued_flops(const ConvShape &c, bool pool) {
+    constexpr int T = K == W43_SPLIT3 ? 128 : 64;
+    const W43Plan p = w43_plan(K, c, pool);
+    return p.ok && p.grid > 0 ? 3.0 * 2.0 * (double)p.items * (c.Cout / T) * (double)T * (double)T * 36.0 * c.Cin : 0.0;
+}
+
+// workgroups of the six-sweep kernel that have work (pixel-block quads x 128-cout tiles): below about one per CU the two-sweep
+// kernel's four times as many, four times shorter workgroups finish sooner (stito_cnn14_forward's choice per call)
+int64_t wino43_split3_workgroups(const ConvShape &c, bool pool) {
+    const W43Plan p = w43_plan(W43_SPLIT3, c, pool);
+    return p.ok ? p.items * (c.Cout / 128) : 0;
+}
+
+// The launch of one of them: the shapes it covers, the workspace it needs, then launch(TTW, POOL) with the plan
 template <class L>
-static int w43_ws_launch(const ConvAlgo &algo, const char *family, const char *covers, const ConvArgs &a, L &&launch) {
+static int w43_ws_launch(W43Kind k, const ConvAlgo &algo, const char *family, const char *covers, const ConvArgs &a, L &&launch) {
     const ConvShape &c = a.c;
-    STITO_REQUIRE(algo.supported(c, a.pool), STITO_E_UNSUPPORTED, "%s: %dx%d map, %d -> %d channels not covered (%s)", family, c.H, c.W, c.Cin,
-                  c.Cout, covers);
-    const size_t need = algo.workspace_bytes(c, a.pool);
-    STITO_REQUIRE(need > 0 && a.ws != nullptr && a.ws_bytes >= need, STITO_E_WORKSPACE, "%s: workspace have %zu need %zu", algo.name, a.ws_bytes, need);
-    return w43_dispatch(c, a.pool, launch);
+    const W43Plan p = w43_plan(k, c, a.pool);
+    STITO_REQUIRE(p.ok, STITO_E_UNSUPPORTED, "%s: %dx%d map, %d -> %d channels not covered (%s)", family, c.H, c.W, c.Cin, c.Cout, covers);
+    STITO_REQUIRE(p.total > 0 && a.ws != nullptr && a.ws_bytes >= p.total, STITO_E_WORKSPACE, "%s: workspace have %zu need %zu", algo.name, a.ws_bytes,
+                  p.total);
+    return w43_dispatch(c, a.pool, [&](auto ttw, auto pool) { return launch(ttw, pool, p); });
+}
+
+// the geometry the conv kernel behind the transform pass takes
+static Wino43Geom w43_conv_geom(const W43Plan &p, const ConvArgs &a) {
+    Wino43Geom g = p.g;
+    g.n_mblocks = (int)p.items;
+    g.ct_group = p.ct_group;
+    g.xcd_m = p.xcd_m;
+    g.amax_out = a.amax_out;
+    return g;
 }
 
 // Hoisted input transform (MODE 2 then MODE 1): V slabs [pixel block][cin/4][36][pair][32][2] in the workspace.
-static size_t wino43_pre_workspace_bytes(const ConvShape &c, bool pool) {
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    if (!wino43_supported(c, pool) || !w43_geometry_any(c, pool, g, lds, blocks)) return 0;
-    return (size_t)(blocks / (c.Cout / 64)) * (size_t)(c.Cin / W43_K) * W43_V * sizeof(float);
-}
-
 template <int TTW, bool POOL>
-static int launch_w43_pre(const ConvArgs &a) {
-    const ConvShape &c = a.c;
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
-    const int64_t m_blocks = blocks / (c.Cout / 64);
-    STITO_TRY((w43_transform<TTW, POOL, 2>(g, m_blocks, a.in, nullptr, a.ws, a.st)));
+static int launch_w43_pre(const ConvArgs &a, const W43Plan &p) {
+    STITO_REQUIRE(p.grid > 0, STITO_E_UNSUPPORTED, "conv (hoisted input transform): cout %d", a.c.Cout);
+    STITO_REQUIRE(p.grid < (1ll << 31), STITO_E_UNSUPPORTED, "conv (hoisted input transform): grid");
+    char *ws = (char *)a.ws;
+    STITO_TRY((w43_transform<TTW, POOL, 2>(p.g, p.v_blocks, a.in, nullptr, ws + p.v.off, a.st)));
     auto kern = k_conv_wino43<TTW, POOL, false, 1>;
     const size_t lds1 = (size_t)2 * W43_BUF * sizeof(float);
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    // grid in whole XCD rounds: 8 XCDs x (groups of 8 pixel blocks) x (groups of 4 channel tiles) x 32 workgroups
-    g.n_mblocks = (int)m_blocks;
-    // channel tiles side by side on an XCD: swept 1..32 at 512 streams (tools/conv_bench.py --modes 9): 4 is best for 8 tiles
-    // (conv_block4: 3.17 / 5.69 ms against 3.63 / 6.59 for 1), 8 from 16 tiles up (1-4 % over 4), 32 loses 15 % at 32 tiles
-    const int n_tiles = c.Cout / 64;
-    const int ag = n_tiles >= 16 ? 8 : 4;
-    STITO_REQUIRE(n_tiles % ag == 0, STITO_E_UNSUPPORTED, "conv (hoisted input transform): cout %d", c.Cout);
-    g.ct_group = ag;
-    g.amax_out = a.amax_out;
-    const int bm = 32 / ag;
-    const int64_t m_groups = ((m_blocks + 7) / 8 + bm - 1) / bm;
-    blocks = 8 * m_groups * (n_tiles / ag) * 32;
-    STITO_REQUIRE(blocks < (1ll << 31), STITO_E_UNSUPPORTED, "conv (hoisted input transform): grid");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W43_THREADS), lds1, a.st, (const float *)a.ws, a.w, a.scale, a.shift, a.out, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(W43_THREADS), lds1, a.st, (const float *)(ws + p.v.off), a.w, a.scale, a.shift, a.out,
+                       w43_conv_geom(p, a));
     STITO_LAUNCH_CHECK();
     return STITO_OK;
 }
 
 // Split-precision variant of the hoisted path: stream maxima -> MODE 3 (V slabs as scaled f16 halves) -> k_conv_wino43s.
-// Workspace: the V slabs (the same bytes as MODE 2's) followed by one unsigned per stream.
-static bool wino43_split_supported(const ConvShape &c, bool pool) {
-    return c.Cin % 64 == 0 && c.Cout % 256 == 0 && wino43_supported(c, pool) && ((int64_t)c.Cin * c.H * c.W) % 8 == 0;
-}
-
-static size_t wino43_split_workspace_bytes(const ConvShape &c, bool pool) {
-    if (!wino43_split_supported(c, pool)) return 0;
-    return align_up(wino43_pre_workspace_bytes(c, pool), 256) + align_up((size_t)c.S * sizeof(unsigned), 256);
-}
-
 template <int TTW, bool POOL>
-static int launch_w43_split(const ConvArgs &a) {
+static int launch_w43_split(const ConvArgs &a, const W43Plan &p) {
     const ConvShape &c = a.c;
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
-    const int64_t m_blocks = blocks / (c.Cout / 64);
+    STITO_REQUIRE(p.grid > 0, STITO_E_UNSUPPORTED, "conv (split-precision winograd): cout %d", c.Cout);
+    STITO_REQUIRE(p.grid < (1ll << 31), STITO_E_UNSUPPORTED, "conv (split-precision winograd): grid");
     char *ws = (char *)a.ws;
     const unsigned *amax;
-    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + align_up((size_t)m_blocks * (c.Cin / W43_K) * W43_V * sizeof(float), 256)), amax));
-    STITO_TRY((w43_transform<TTW, POOL, 3>(g, m_blocks, a.in, amax, ws, a.st)));
+    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + p.amax.off), amax));
+    STITO_TRY((w43_transform<TTW, POOL, 3>(p.g, p.v_blocks, a.in, amax, ws + p.v.off, a.st)));
     auto kern = k_conv_wino43s<TTW, POOL>;
     const size_t lds1 = (size_t)3 * S43_SLAB;
     static_assert((size_t)12 * 32 * W43_XT * sizeof(float) <= (size_t)3 * S43_SLAB, "epilogue exchange fits the slab ring");
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    g.n_mblocks = (int)m_blocks;
-    const int n_tiles = c.Cout / 64;
-    int ag = n_tiles >= 16 ? 8 : (n_tiles >= 8 ? 4 : 2);  // swept again with the round's final kernels (profiles/round3_stream_loop_experiments.txt, 15.)
-    if (const char *e = getenv("STITO_W43S_CTG")) { const int ae = atoi(e); if (ae >= 1 && ae <= 32 && (ae & (ae - 1)) == 0 && n_tiles % ae == 0) ag = ae; }  // tuning aid (tools/conv_bench.py)
-    STITO_REQUIRE(ag >= 1 && ag <= 32 && (ag & (ag - 1)) == 0 && n_tiles % ag == 0, STITO_E_UNSUPPORTED, "conv (split-precision winograd): cout %d", c.Cout);
-    g.ct_group = ag;
-    const int bm = 32 / ag;
-    const int64_t m_groups = ((m_blocks + 7) / 8 + bm - 1) / bm;
-    blocks = 8 * m_groups * (n_tiles / ag) * 32;
-    STITO_REQUIRE(blocks < (1ll << 31), STITO_E_UNSUPPORTED, "conv (split-precision winograd): grid");
-    g.amax_out = a.amax_out;
+    Wino43Geom g = w43_conv_geom(p, a);
     const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
     W43_CLK_ARM(g)
     // the layer as several grids on several hardware queues (w43_multi_queue_launch): the queues' dispatchers overlap the hand-over
-    STITO_TRY(w43_multi_queue_launch(blocks, a.st, [&](int64_t n_blk, int b0, hipStream_t q) {
+    STITO_TRY(w43_multi_queue_launch(p.grid, a.st, [&](int64_t n_blk, int b0, hipStream_t q) {
         Wino43Geom gq = g;
         gq.b0 = b0;
-        hipLaunchKernelGGL(kern, dim3((unsigned)n_blk), dim3(W43_THREADS), lds1, q, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, gq,
-                           amax, u_inv);
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_blk), dim3(W43_THREADS), lds1, q, (const char *)(ws + p.v.off), (const char *)a.w, a.scale, a.shift,
+                           a.out, gq, amax, u_inv);
     }));
     STITO_LAUNCH_CHECK();
     W43_CLK_REPORT("k_conv_wino43s (f16 MFMA)", c, a.st)
     return STITO_OK;
 }
 
-// Two-sweep variant: workspace = V slabs of the pixel-block pairs | stream maxima | per-workgroup partial outputs (256 KB each).
-// -> the grid of ONE sweep set (SWSPLIT launches twice as many); xcd_m / ct_group: the kernel's workgroup order
-template <int TTW>
-static int64_t w43_split2_grid(const ConvShape &c, bool pool, int64_t &m_pairs, int &ct_group, int &xcd_m) {
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    if (!w43_geometry<TTW>(c, pool, g, lds, blocks)) return 0;
-    const int64_t m_blocks = blocks / (c.Cout / 64);
-    m_pairs = (m_blocks + 1) / 2;
-    const int n_tiles_all = c.Cout / 64;   // a multiple of 4 (wino43_split_supported)
-    // XCD split: the xm in {8, 4, 2, 1} with the fewest slab streams per L2, pairs / xm + tiles / (8 / xm); 8 on a tie
-    int xm = 8;
-    for (int cand = 4; cand >= 1; cand >>= 1)
-        if (n_tiles_all % (8 / cand) == 0 && (m_pairs + cand - 1) / cand + n_tiles_all / (8 / cand) < (m_pairs + xm - 1) / xm + n_tiles_all / (8 / xm)) xm = cand;
-    if (const char *e = getenv("STITO_W43S2_XM")) { const int xe = atoi(e); if ((xe == 8 || xe == 4 || xe == 2 || xe == 1) && n_tiles_all % (8 / xe) == 0) xm = xe; }  // tuning aid
-    xcd_m = xm;
-    const int n_tiles = n_tiles_all / (8 / xm);
-    int a = 8;
-    while (a > 1 && n_tiles % a != 0) a >>= 1;
-    if (const char *e = getenv("STITO_W43S_CTG")) { const int ae = atoi(e); if (ae >= 1 && ae <= 32 && (ae & (ae - 1)) == 0 && n_tiles % ae == 0) a = ae; }
-    if (a < 1 || a > 32 || (a & (a - 1)) != 0 || n_tiles % a != 0) return 0;
-    ct_group = a;
-    const int bm = 32 / a;
-    const int64_t m_groups = ((m_pairs + xm - 1) / xm + bm - 1) / bm;
-    return 8 * m_groups * (n_tiles / a) * 32;
+// The conv kernel of the two- / six-sweep variant behind its stream maxima and its transform pass (MODE 4 / 5): `whole` runs an
+// item's sweeps in one workgroup; with `split`, `each` runs them as `sweeps` workgroups -- so many grids -- that hand over through
+// the item's flag or count, zeroed here.
+template <int TTW, bool POOL, int MODE, class K>
+static int w43_launch_sweeps(const ConvArgs &a, const W43Plan &p, K whole, K each, bool split, int sweeps) {
+    const ConvShape &c = a.c;
+    char *ws = (char *)a.ws;
+    const unsigned *amax;
+    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + p.amax.off), amax));
+    STITO_TRY((w43_transform<TTW, POOL, MODE>(p.g, p.v_blocks, a.in, amax, ws + p.v.off, a.st)));
+    const size_t lds1 = (size_t)3 * S43B_SLAB;
+    static_assert((size_t)12 * 32 * W43_XT * sizeof(float) <= (size_t)3 * S43B_SLAB, "epilogue exchange fits the slab ring");
+    Wino43Geom g = w43_conv_geom(p, a);
+    const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
+    unsigned *flags = (unsigned *)(ws + p.flags.off);
+    W43_CLK_ARM(g)
+    if (split) STITO_TRY(zero_async(flags, p.flags.bytes, a.st));
+    const K kern = split ? each : whole;
+    STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    hipLaunchKernelGGL(kern, dim3((unsigned)((split ? sweeps : 1) * p.grid)), dim3(W43_THREADS), lds1, a.st, (const char *)(ws + p.v.off),
+                       (const char *)a.w, a.scale, a.shift, a.out, g, amax, u_inv, (f32x4 *)(ws + p.partial.off), flags);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
 }
 
-static int64_t w43_split2_grid_any(const ConvShape &c, bool pool, int64_t &m_pairs, int &ct_group) {
-    int xm;
-    return w43_dispatch(c, pool, [&](auto ttw, auto) { return w43_split2_grid<decltype(ttw)::value>(c, pool, m_pairs, ct_group, xm); });
-}
-
-// the two sweeps of an item as two workgroups when that still fits one round of the device (see the kernel); STITO_W43S2_SWSPLIT=0 / 1 forces
+// Two-sweep variant (k_conv_wino43s2).  The two sweeps of an item as two workgroups when that still fits one round of the device
+// (see the kernel); STITO_W43S2_SWSPLIT=0 / 1 forces.
 // Measured (tools/small_conv_ab.sh, 64 / 128 streams x 257 frames): 1024 -> 1024 0.348 -> 0.293 ms, 1024 -> 2048 0.346 -> 0.231, 2048 -> 2048
 // 0.640 -> 0.388; with 512 input channels the halves are too short to carry the second workgroup's prologue and its wait
 // (512 -> 1024: 0.201 -> 0.236), hence the channel threshold.
@@ -1846,193 +1927,31 @@ static bool w43_split2_sweep_split(int64_t m_pairs, int cout, int cin) {
     return cin >= 1024 && 2 * m_pairs * (cout / 64) <= d.cus;
 }
 
-// f16-pipe FLOPs the two-sweep kernel issues: pixel-block pairs (a padded half included) x channel tiles x 64 x 64 x 36 x cin x 3 products
-static double wino43_split2_issued_flops(const ConvShape &c, bool pool) {
-    if (!wino43_split_supported(c, pool)) return 0.0;
-    int64_t m_pairs = 0;
-    int a;
-    if (w43_split2_grid_any(c, pool, m_pairs, a) <= 0) return 0.0;
-    return 3.0 * 2.0 * (double)m_pairs * (c.Cout / 64) * 64.0 * 64.0 * 36.0 * c.Cin;
-}
-
-static size_t wino43_split2_workspace_bytes(const ConvShape &c, bool pool) {
-    if (!wino43_split_supported(c, pool)) return 0;
-    int64_t m_pairs = 0;
-    int a;
-    const int64_t grid = w43_split2_grid_any(c, pool, m_pairs, a);
-    if (grid <= 0 || grid >= (1ll << 31)) return 0;
-    return align_up((size_t)m_pairs * 2 * (size_t)(c.Cin / 16) * 3 * S43B_PART, 256) + align_up((size_t)c.S * sizeof(unsigned), 256) +
-           (size_t)grid * 2 * 16 * W43_THREADS * sizeof(f32x4) + align_up((size_t)grid * sizeof(unsigned), 256);   // ... + one flag per workgroup item (SWSPLIT)
-}
-
 template <int TTW, bool POOL>
-static int launch_w43_split2(const ConvArgs &a) {
+static int launch_w43_split2(const ConvArgs &a, const W43Plan &p) {
     const ConvShape &c = a.c;
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
-    int64_t m_pairs = 0;
-    int ag = 4, xm = 8;
-    const int64_t grid = w43_split2_grid<TTW>(c, POOL, m_pairs, ag, xm);
-    STITO_REQUIRE(grid > 0 && grid < (1ll << 30), STITO_E_UNSUPPORTED, "conv (two-sweep split-precision winograd): grid / cout %d", c.Cout);
-    char *ws = (char *)a.ws;
-    const size_t vbytes = align_up((size_t)m_pairs * 2 * (size_t)(c.Cin / 16) * 3 * S43B_PART, 256);
-    f32x4 *partial = (f32x4 *)(ws + vbytes + align_up((size_t)c.S * sizeof(unsigned), 256));
-    const unsigned *amax;
-    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + vbytes), amax));
-    STITO_TRY((w43_transform<TTW, POOL, 4>(g, 2 * m_pairs, a.in, amax, ws, a.st)));   // V slabs of 2 * m_pairs pixel blocks
-    const bool swsplit = w43_split2_sweep_split(m_pairs, c.Cout, c.Cin);
-    unsigned *flags = (unsigned *)((char *)partial + (size_t)grid * 2 * 16 * W43_THREADS * sizeof(f32x4));
-    const size_t lds1 = (size_t)3 * S43B_SLAB;
-    static_assert((size_t)12 * 32 * W43_XT * sizeof(float) <= (size_t)3 * S43B_SLAB, "epilogue exchange fits the slab ring");
-    g.n_mblocks = (int)m_pairs;
-    g.ct_group = ag;
-    g.xcd_m = xm;
-    g.amax_out = a.amax_out;
-    const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
-    W43_CLK_ARM(g)
-    if (swsplit) {
-        STITO_TRY(zero_async(flags, (size_t)grid * sizeof(unsigned), a.st));
-        auto kern = k_conv_wino43s2<TTW, POOL, true>;
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(2 * grid)), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
-                           amax, u_inv, partial, flags);
-    } else {
-        auto kern = k_conv_wino43s2<TTW, POOL, false>;
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
-                           amax, u_inv, partial, flags);
-    }
-    STITO_LAUNCH_CHECK();
+    STITO_REQUIRE(p.grid > 0 && p.grid < (1ll << 30), STITO_E_UNSUPPORTED, "conv (two-sweep split-precision winograd): grid / cout %d", c.Cout);
+    STITO_TRY((w43_launch_sweeps<TTW, POOL, 4>(a, p, k_conv_wino43s2<TTW, POOL, false>, k_conv_wino43s2<TTW, POOL, true>,
+                                               w43_split2_sweep_split(p.items, c.Cout, c.Cin), 2)));
     W43_CLK_REPORT("k_conv_wino43s2 (f16 MFMA)", c, a.st)
     return STITO_OK;
 }
 
-// Six-sweep variant (k_conv_wino43s3): workspace = V slabs of the pixel-block quads | stream maxima | per-workgroup partial outputs (1 MB each).
-static int64_t w43_split3_grid_any(const ConvShape &c, bool pool, int64_t &m_quads, int &ct_group);
-static bool wino43_split3_supported(const ConvShape &c, bool pool) {
-    if (!(c.Cin % 64 == 0 && c.Cout % 512 == 0 && wino43_supported(c, pool) && ((int64_t)c.Cin * c.H * c.W) % 8 == 0)) return false;
-    int64_t m_quads = 0;
-    int a;
-    const int64_t grid = w43_split3_grid_any(c, pool, m_quads, a);   // "supported" means the launcher finds a grid for it
-    return grid > 0 && grid < (1ll << 31);
-}
-
-template <int TTW>
-static int64_t w43_split3_grid(const ConvShape &c, bool pool, int64_t &m_quads, int &ct_group, int &xcd_m) {
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    if (!w43_geometry<TTW>(c, pool, g, lds, blocks)) return 0;
-    const int64_t m_blocks = blocks / (c.Cout / 64);
-    m_quads = (m_blocks + 3) / 4;
-    const int n_tiles_all = c.Cout / 128;   // a multiple of 4 (wino43_split3_supported)
-    // XCD split (see the kernel): the xm in {8, 4, 2} with the fewest slab bytes per L2, quads / xm + tiles / (8 / xm); 8 on a tie
-    int xm = 8;
-    for (int cand = 4; cand >= 2; cand >>= 1)
-        if (n_tiles_all % (8 / cand) == 0 && (m_quads + cand - 1) / cand + n_tiles_all / (8 / cand) < (m_quads + xm - 1) / xm + n_tiles_all / (8 / xm)) xm = cand;
-    if (const char *e = getenv("STITO_W43S3_XM")) { const int xe = atoi(e); if ((xe == 8 || xe == 4 || xe == 2) && n_tiles_all % (8 / xe) == 0) xm = xe; }  // tuning aid
-    xcd_m = xm;
-    const int n_tiles = n_tiles_all / (8 / xm);
-    const int64_t mq_loc = (m_quads + xm - 1) / xm;
-    // channel tiles side by side in a round of 32 workgroups: a power of two that divides the tile count (cout 1536 has 12 tiles,
-    // 6 per XCD half: ADVICE r5), grown while a round is not full
-    int a = 4;
-    while (a > 1 && n_tiles % a != 0) a >>= 1;
-    while (a < n_tiles && a < 32 && 32 / a > mq_loc && n_tiles % (2 * a) == 0) a *= 2;
-    if (const char *e = getenv("STITO_W43S3_CTG")) { const int ae = atoi(e); if (ae >= 1 && ae <= 32 && (ae & (ae - 1)) == 0 && n_tiles % ae == 0) a = ae; }
-    if (n_tiles % a != 0) return 0;
-    ct_group = a;
-    const int bm = 32 / a;
-    const int64_t m_groups = (mq_loc + bm - 1) / bm;
-    return 8 * m_groups * (n_tiles / a) * 32;
-}
-
-static int64_t w43_split3_grid_any(const ConvShape &c, bool pool, int64_t &m_quads, int &ct_group) {
-    int xm;
-    return w43_dispatch(c, pool, [&](auto ttw, auto) { return w43_split3_grid<decltype(ttw)::value>(c, pool, m_quads, ct_group, xm); });
-}
-
-// f16-pipe FLOPs the six-sweep kernel issues: pixel-block quads (padded blocks included) x 128-cout tiles x 128 x 128 x 36 x cin x 3 products
-static double wino43_split3_issued_flops(const ConvShape &c, bool pool) {
-    if (!wino43_split3_supported(c, pool)) return 0.0;
-    int64_t m_quads = 0;
-    int a;
-    if (w43_split3_grid_any(c, pool, m_quads, a) <= 0) return 0.0;
-    return 3.0 * 2.0 * (double)m_quads * (c.Cout / 128) * 128.0 * 128.0 * 36.0 * c.Cin;
-}
-
-// workgroups of the six-sweep kernel that have work (pixel-block quads x 128-cout tiles): below about one per CU the two-sweep
-// kernel's four times as many, four times shorter workgroups finish sooner (stito_cnn14_forward's choice per call)
-int64_t wino43_split3_workgroups(const ConvShape &c, bool pool) {
-    if (!wino43_split3_supported(c, pool)) return 0;
-    int64_t m_quads = 0;
-    int a;
-    if (w43_split3_grid_any(c, pool, m_quads, a) <= 0) return 0;
-    return m_quads * (c.Cout / 128);
-}
-
-static size_t w43_split3_vbytes(const ConvShape &c, int64_t m_quads) { return align_up((size_t)m_quads * 6 * (size_t)(c.Cin >> 3) * S43B_PART, 256); }
-
-static size_t wino43_split3_workspace_bytes(const ConvShape &c, bool pool) {
-    if (!wino43_split3_supported(c, pool)) return 0;
-    int64_t m_quads = 0;
-    int a;
-    const int64_t grid = w43_split3_grid_any(c, pool, m_quads, a);
-    if (grid <= 0 || grid >= (1ll << 31)) return 0;
-    return w43_split3_vbytes(c, m_quads) + align_up((size_t)c.S * sizeof(unsigned), 256) + (size_t)grid * (8 * 2 * 4 * 20 * 64) * sizeof(f32x4) +
-           align_up((size_t)grid * sizeof(unsigned), 256);   // ... + one row count per workgroup item (SWSPLIT)
-}
-
-// the six sweeps of an item as six workgroups: OFF unless STITO_W43S3_SWSPLIT=1.  Built and measured in round 6 for the small batches
-// whose items alone leave CUs idle (tools/small_conv_ab.sh, profiles/round6_small_conv_ab.txt): it takes 64-stream conv_block6.conv2 from
-// 1.53 to 0.51 ms -- but the two-sweep kernel with ITS sweeps split does the same layer in 0.39 (the six-sweep kernel's transform pass and
-// its 1 MB of partial outputs per item do not shrink with the batch), and that is what stito_cnn14_forward takes for small batches.
-static bool w43_split3_sweep_split(int64_t, int) {
-    if (const char *e = getenv("STITO_W43S3_SWSPLIT")) return atoi(e) != 0;   // (read per launch: the tests flip it)
-    return false;
+// Six-sweep variant (k_conv_wino43s3).  The six sweeps of an item as six workgroups: OFF unless STITO_W43S3_SWSPLIT=1.  Built and
+// measured in round 6 for the small batches whose items alone leave CUs idle (tools/small_conv_ab.sh, profiles/round6_small_conv_ab.txt):
+// it takes 64-stream conv_block6.conv2 from 1.53 to 0.51 ms -- but the two-sweep kernel with ITS sweeps split does the same layer in 0.39
+// (the six-sweep kernel's transform pass and its 1.25 MB of partial outputs per item do not shrink with the batch), and that is what
+// stito_cnn14_forward takes for small batches.
+static bool w43_split3_sweep_split() {
+    const char *e = getenv("STITO_W43S3_SWSPLIT");   // (read per launch: the tests flip it)
+    return e != nullptr && atoi(e) != 0;
 }
 
 template <int TTW, bool POOL>
-static int launch_w43_split3(const ConvArgs &a) {
-    const ConvShape &c = a.c;
-    Wino43Geom g;
-    size_t lds;
-    int64_t blocks;
-    STITO_TRY(w43_staging<TTW>(c, POOL, g, lds, blocks));
-    int64_t m_quads = 0;
-    int ag = 4, xm = 8;
-    const int64_t grid = w43_split3_grid<TTW>(c, POOL, m_quads, ag, xm);
-    STITO_REQUIRE(grid > 0 && grid < (1ll << 31), STITO_E_UNSUPPORTED, "conv (six-sweep split-precision winograd): grid / cout %d", c.Cout);
-    char *ws = (char *)a.ws;
-    const size_t vbytes = w43_split3_vbytes(c, m_quads);
-    f32x4 *partial = (f32x4 *)(ws + vbytes + align_up((size_t)c.S * sizeof(unsigned), 256));
-    const unsigned *amax;
-    STITO_TRY(w43_stream_amax(a, (unsigned *)(ws + vbytes), amax));
-    STITO_TRY((w43_transform<TTW, POOL, 5>(g, 4 * m_quads, a.in, amax, ws, a.st)));   // V slabs of 4 * m_quads pixel blocks
-    const size_t lds1 = (size_t)3 * S43B_SLAB;
-    g.n_mblocks = (int)m_quads;
-    g.ct_group = ag;
-    g.xcd_m = xm;
-    g.amax_out = a.amax_out;
-    const float *u_inv = a.w + (size_t)36 * c.Cout * c.Cin + 1;
-    unsigned *counts = (unsigned *)((char *)partial + (size_t)grid * (8 * 2 * 4 * 20 * 64) * sizeof(f32x4));
-    W43_CLK_ARM(g)
-    if (w43_split3_sweep_split(m_quads, c.Cout) && 6 * grid < (1ll << 31)) {
-        STITO_TRY(zero_async(counts, (size_t)grid * sizeof(unsigned), a.st));
-        auto kern = k_conv_wino43s3<TTW, POOL, true>;
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(6 * grid)), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
-                           amax, u_inv, partial, counts);
-    } else {
-        auto kern = k_conv_wino43s3<TTW, POOL, false>;
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W43_THREADS), lds1, a.st, (const char *)ws, (const char *)a.w, a.scale, a.shift, a.out, g,
-                           amax, u_inv, partial, counts);
-    }
-    STITO_LAUNCH_CHECK();
-    W43_CLK_REPORT("k_conv_wino43s3 (f16 MFMA)", c, a.st)
+static int launch_w43_split3(const ConvArgs &a, const W43Plan &p) {
+    STITO_TRY((w43_launch_sweeps<TTW, POOL, 5>(a, p, k_conv_wino43s3<TTW, POOL, false>, k_conv_wino43s3<TTW, POOL, true>,
+                                               w43_split3_sweep_split() && 6 * p.grid < (1ll << 31), 6)));
+    W43_CLK_REPORT("k_conv_wino43s3 (f16 MFMA)", a.c, a.st)
     return STITO_OK;
 }
 
@@ -2048,15 +1967,6 @@ static int pack_wino43(const float *w_oihw, int cout, int cin, float *packed, hi
     return STITO_OK;
 }
 
-// its workgroup order deals channel tiles in fours / eights
-static bool wino43_pre_supported(const ConvShape &c, bool pool) {
-    return c.Cout % 256 == 0 && (c.Cout < 1024 || c.Cout % 512 == 0) && wino43_supported(c, pool);
-}
-
-static bool wino43_split01_supported(const ConvShape &c, bool pool) {   // k_conv_wino43s / s2
-    return (c.Cout < 1024 || c.Cout % 512 == 0) && wino43_split_supported(c, pool);
-}
-
 static constexpr const char *W43S_FAMILY = "conv (split-precision winograd F(4x4,3x3))", *W43S_COVERS = "cin % 64, cout % 256";
 
 const ConvAlgo &wino43_algo() {
@@ -2069,28 +1979,28 @@ const ConvAlgo &wino43_algo() {
     return e;
 }
 
+// (the hoisted and the split-precision kernel issue the f32 kernel's MFMAs, the latter three f16 products for each: wino43_issued_flops)
 const ConvAlgo &wino43_pre_algo() {
     static const ConvAlgo e = {
         .name = "conv (winograd F(4x4,3x3), hoisted input transform)", .winograd = true, .reports_amax = true,
-        .same_packing = STITO_CONV_WINOGRAD_F4, .supported = wino43_pre_supported, .packed_floats = w43_packed_floats, .pack = pack_wino43,
-        .issued_flops = wino43_issued_flops, .workspace_bytes = wino43_pre_workspace_bytes, .launch = [](const ConvArgs &a) {
+        .same_packing = STITO_CONV_WINOGRAD_F4, .supported = w43_supported<W43_PRE>, .packed_floats = w43_packed_floats, .pack = pack_wino43,
+        .issued_flops = wino43_issued_flops, .workspace_bytes = w43_workspace_bytes<W43_PRE>, .launch = [](const ConvArgs &a) {
             STITO_REQUIRE(a.c.Cin % 8 == 0 && a.c.Cout % 64 == 0, STITO_E_UNSUPPORTED, "conv (winograd): cin %d / cout %d", a.c.Cin, a.c.Cout);
-            return w43_ws_launch(wino43_pre_algo(), wino43_pre_algo().name, "cout must be a multiple of 256", a, [&](auto ttw, auto pool) {
-                return launch_w43_pre<decltype(ttw)::value, decltype(pool)::value>(a);
-            });
+            return w43_ws_launch(W43_PRE, wino43_pre_algo(), wino43_pre_algo().name, "cout must be a multiple of 256", a,
+                                 [&](auto ttw, auto pool, const W43Plan &p) { return launch_w43_pre<decltype(ttw)::value, decltype(pool)::value>(a, p); });
         }};
     return e;
 }
 
 const ConvAlgo &wino43_split_algo() {
     static const ConvAlgo e = {
-        .name = W43S_FAMILY, .winograd = true, .reads_amax = true, .reports_amax = true, .supported = wino43_split01_supported,
+        .name = W43S_FAMILY, .winograd = true, .reads_amax = true, .reports_amax = true, .supported = w43_supported<W43_SPLIT>,
         .packed_floats = w43s_packed_floats,
         .pack = [](const float *w, int cout, int cin, float *packed, hipStream_t st) { return pack_wino43_split(w, cout, cin, packed, 0, st); },
         .issued_flops = [](const ConvShape &c, bool pool) { return 3.0 * wino43_issued_flops(c, pool); },   // hi hi' + hi lo' + lo hi' on the f16 pipe
-        .workspace_bytes = wino43_split_workspace_bytes, .launch = [](const ConvArgs &a) {
-            return w43_ws_launch(wino43_split_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool) {
-                return launch_w43_split<decltype(ttw)::value, decltype(pool)::value>(a);
+        .workspace_bytes = w43_workspace_bytes<W43_SPLIT>, .launch = [](const ConvArgs &a) {
+            return w43_ws_launch(W43_SPLIT, wino43_split_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool, const W43Plan &p) {
+                return launch_w43_split<decltype(ttw)::value, decltype(pool)::value>(a, p);
             });
         }};
     return e;
@@ -2099,11 +2009,11 @@ const ConvAlgo &wino43_split_algo() {
 const ConvAlgo &wino43_split2_algo() {
     static const ConvAlgo e = {
         .name = "conv (two-sweep split-precision winograd F(4x4,3x3))", .winograd = true, .reads_amax = true, .reports_amax = true,
-        .supported = wino43_split01_supported, .packed_floats = w43s_packed_floats,
+        .supported = w43_supported<W43_SPLIT2>, .packed_floats = w43s_packed_floats,
         .pack = [](const float *w, int cout, int cin, float *packed, hipStream_t st) { return pack_wino43_split(w, cout, cin, packed, 1, st); },
-        .issued_flops = wino43_split2_issued_flops, .workspace_bytes = wino43_split2_workspace_bytes, .launch = [](const ConvArgs &a) {
-            return w43_ws_launch(wino43_split2_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool) {
-                return launch_w43_split2<decltype(ttw)::value, decltype(pool)::value>(a);
+        .issued_flops = w43_sweeps_issued_flops<W43_SPLIT2>, .workspace_bytes = w43_workspace_bytes<W43_SPLIT2>, .launch = [](const ConvArgs &a) {
+            return w43_ws_launch(W43_SPLIT2, wino43_split2_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool, const W43Plan &p) {
+                return launch_w43_split2<decltype(ttw)::value, decltype(pool)::value>(a, p);
             });
         }};
     return e;
@@ -2112,11 +2022,11 @@ const ConvAlgo &wino43_split2_algo() {
 const ConvAlgo &wino43_split3_algo() {
     static const ConvAlgo e = {
         .name = "conv (six-sweep split-precision winograd F(4x4,3x3))", .winograd = true, .reads_amax = true, .reports_amax = true,
-        .supported = wino43_split3_supported, .packed_floats = w43s_packed_floats,
+        .supported = w43_supported<W43_SPLIT3>, .packed_floats = w43s_packed_floats,
         .pack = [](const float *w, int cout, int cin, float *packed, hipStream_t st) { return pack_wino43_split(w, cout, cin, packed, 2, st); },
-        .issued_flops = wino43_split3_issued_flops, .workspace_bytes = wino43_split3_workspace_bytes, .launch = [](const ConvArgs &a) {
-            return w43_ws_launch(wino43_split3_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool) {
-                return launch_w43_split3<decltype(ttw)::value, decltype(pool)::value>(a);
+        .issued_flops = w43_sweeps_issued_flops<W43_SPLIT3>, .workspace_bytes = w43_workspace_bytes<W43_SPLIT3>, .launch = [](const ConvArgs &a) {
+            return w43_ws_launch(W43_SPLIT3, wino43_split3_algo(), W43S_FAMILY, W43S_COVERS, a, [&](auto ttw, auto pool, const W43Plan &p) {
+                return launch_w43_split3<decltype(ttw)::value, decltype(pool)::value>(a, p);
             });
         }};
     return e;
