@@ -108,7 +108,8 @@ const char *stito_last_error(void);
 int stito_version(void);
 /* Additions since the last change of stito_version() that leave every existing symbol and struct as it is (a caller built against
  * 10.0 runs unchanged): 1 = stito_gather_crops; 2 = STITO_FX_DASP_EQ, _DASP_COMPRESSOR, _DASP_DISTORTION (kinds 8 - 10 of
- * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits). */
+ * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits); 3 = stito_barkspectrum_mixed,
+ * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -450,6 +451,38 @@ size_t stito_spectral_centroid_workspace_bytes(int n_items, int channels, int64_
 int stito_spectral_centroid(const float *audio_dev, int n_items, int channels, int64_t n_samples, double sample_rate,
                             const float *window_dev, const float *twiddle_dev, float *out_dev, void *workspace_dev,
                             size_t workspace_bytes, void *stream);
+
+/* ---- bark spectrum at any 7-smooth FFT size (ABI 10.3; csrc/fft_mixed.hip) -------------------------------------------------- */
+/* The same quantity as stito_barkspectrum for an even fft_size in [128, 96000] whose prime factors all lie in {2, 3, 5, 7}
+ * (44 100, 48 000, 22 050, 32 000, 88 200, 96 000, ...; powers of two included, though stito_barkspectrum keeps serving them).
+ * The reference's MIR metric calls compute_barkspectrum(x, sample_rate, mode="mono") (utils.py:83), which binds the sample
+ * rate to fft_size: this entry is what makes that binding computable.
+ *
+ * The real frame is packed as N2 = fft_size / 2 complex points and transformed by the four-step scheme over N2 = na * nb
+ * (nb the largest divisor of N2 not above sqrt(N2), na = N2 / nb <= 512): nb Stockham transforms of length na in LDS, the
+ * twiddle, a transposing store to a workgroup-private slab of N2 complex floats in the workspace, na transforms of length nb
+ * in LDS written back over the slab in natural order, then the E/O unpacking of the real spectrum.  The time mean of |X| is
+ * summed by one owner thread per bin, frames in order, in a private row of the workspace: the same input gives the same
+ * bits on every launch and a row does not depend on the batch around it.
+ *
+ * stito_fft_mixed_plan (host only, touches no device): the factorisation the launch uses.  Returns the number of radices
+ * written to radices[] -- first those of na, then those of nb, each in {2, 3, 4, 5, 7}, the product of each group equal to
+ * *na and *nb, *na * *nb == fft_size / 2 -- or STITO_E_UNSUPPORTED (odd, outside [128, 96000], a prime factor above 7; the
+ * message names the length) or STITO_E_INVALID (max_radices too small, NULL pointers).
+ *
+ * tables_dev: tables_len = na + nb + 2 * N2 complex float32 (re, im), every entry cos / sin taken in float64 and rounded:
+ *   [0, na)                 exp(-2 pi i m / na)                       roots of the length-na transforms
+ *   [na, na + nb)           exp(-2 pi i m / nb)                       roots of the length-nb transforms
+ *   [na + nb, +N2)          exp(-2 pi i (n2 k1 mod N2) / N2) at n2 * na + k1     the four-step twiddle, in the slab's order
+ *   [na + nb + N2, +N2)     exp(-2 pi i k / fft_size), k < N2         the unpacking twiddle
+ * fb_dev, out_dev, mode: as stito_barkspectrum.  n_samples > fft_size / 2 (reflect padding).  The workspace holds, per
+ * (item, signal), the slab and the row of sums; stito_barkspectrum_mixed_workspace_bytes returns 0 for arguments the launch
+ * would refuse.  `stream` is a hipStream_t. */
+int64_t stito_barkspectrum_mixed_workspace_bytes(int n_items, int n_sig, int fft_size);
+int stito_barkspectrum_mixed(const float *audio_dev, int n_items, int channels, int64_t n_samples, int mode, int fft_size,
+                             const void *tables_dev, int64_t tables_len, const float *fb_dev, int n_bands, float *out_dev,
+                             void *ws_dev, int64_t ws_bytes, void *stream);
+int stito_fft_mixed_plan(int fft_size, int *na, int *nb, int *radices, int max_radices);
 
 /* MFCC statistics of get_mfcc_feature_embeds (utils.py:116-159) on top of stito_logmel's 10 log10(mel power):
  * logmel_dev (n_items * channels, T, n_mels); per item: clamp to (max over the item's channels, bands and

@@ -171,6 +171,13 @@ __global__ void k_l2norm_rows(float *__restrict__ x, int n_rows, int n_cols) {
     for (int c = 0; c < n_cols; ++c) p[c] = p[c] / d;
 }
 
+// the launch of k_l2norm_rows for the feature kernels of other files (fft_mixed.hip)
+int l2norm_rows(float *x, int n_rows, int n_cols, hipStream_t st) {
+    hipLaunchKernelGGL(k_l2norm_rows, dim3((n_rows + 63) / 64), dim3(64), 0, st, x, n_rows, n_cols);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
 // per-frame centroids (n_rows, T) -> nan_to_num -> adaptive_avg_pool1d(10) -> / nyquist  => (n_rows, 10)
 __global__ void k_centroid_pool(const float *__restrict__ sc, int n_rows, int64_t T, float nyquist, float *__restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;

@@ -117,6 +117,10 @@ SIGNATURES = {
     "stito_lufs_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
     "stito_lufs": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "stito_barkspectrum": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "stito_barkspectrum_mixed_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "stito_barkspectrum_mixed": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_int64, c_void_p]),
+    "stito_fft_mixed_plan": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int]),
     "stito_spectral_centroid_workspace_bytes": (c_size_t, [c_int, c_int, c_int64]),
     "stito_spectral_centroid": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

@@ -93,14 +93,65 @@ def _gpu(x: torch.Tensor):
     return x.detach().to(dev, torch.float32).contiguous(), dev
 
 
+def fft_mixed_plan(fft_size: int):
+    """(na, nb, radices of na, radices of nb) of the four-step factorisation fft_size / 2 = na * nb that
+    stito_barkspectrum_mixed uses (stito_fft_mixed_plan: host only, no GPU needed).  NotImplementedError for a length
+    that is odd, outside [128, 96000] or has a prime factor above 7."""
+    import ctypes
+
+    na, nb, rad = ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 32)()
+    n = _hip.lib().stito_fft_mixed_plan(int(fft_size), ctypes.byref(na), ctypes.byref(nb), rad, 32)
+    if n < 0:
+        _hip.check(n)
+    rad, ra, prod = list(rad[:n]), [], 1
+    while prod < na.value:
+        ra.append(rad[len(ra)])
+        prod *= ra[-1]
+    return na.value, nb.value, ra, rad[len(ra):]
+
+
+def mixed_tables_host(fft_size: int) -> np.ndarray:
+    """The tables of stito_barkspectrum_mixed (layout: include/stito_hip.h) as (na + nb + 2 N2, 2) float32 (re, im): the
+    roots of the length-na and length-nb transforms, the four-step twiddle exp(-2 pi i n2 k1 / N2) at n2 * na + k1, and
+    the unpacking twiddle exp(-2 pi i k / fft_size).  Angles are reduced in integers, cos / sin taken in float64, then
+    rounded once -- like _twiddle."""
+    na, nb, _, _ = fft_mixed_plan(fft_size)
+    N2 = na * nb
+
+    def roots(idx, n):
+        a = -2.0 * np.pi * (np.asarray(idx, dtype=np.int64) % n).astype(np.float64) / n
+        return np.stack([np.cos(a), np.sin(a)], 1)
+
+    four = np.arange(nb, dtype=np.int64)[:, None] * np.arange(na, dtype=np.int64)[None, :]   # [n2][k1]
+    return np.concatenate([roots(np.arange(na), na), roots(np.arange(nb), nb), roots(four.reshape(-1), N2),
+                           roots(np.arange(N2), fft_size)]).astype(np.float32)
+
+
+def _mixed_tables(fft_size: int, device) -> torch.Tensor:
+    key = ("mixed", fft_size, str(device))
+    if key not in _cache:
+        _cache[key] = torch.from_numpy(mixed_tables_host(fft_size)).to(device).contiguous()
+    return _cache[key]
+
+
+def _is_lds_size(fft_size: int) -> bool:
+    """A power of two in [128, 32768]: the lengths k_stft_feature transforms in LDS."""
+    return not (fft_size & (fft_size - 1)) and 128 <= fft_size <= 32768
+
+
 def compute_barkspectrum(x: torch.Tensor, fft_size: int = 32768, n_bands: int = 24, sample_rate: int = 44100,
-                         f_min: float = 20.0, f_max: float = 20000.0, mode: str = "mid-side", **kwargs):
+                         f_min: float = 20.0, f_max: float = 20000.0, mode: str = "mid-side", mixed_radix: bool = False,
+                         **kwargs):
     """Bark spectrum embedding (bs, n_signals * n_bands), L2-normalised -- reference features.py:166-232.
-    fft_size must be a power of two <= 32768 here (the transform runs in LDS)."""
+    fft_size must be a power of two <= 32768 here (the transform runs in LDS), unless mixed_radix=True: then every even
+    length in [128, 96000] with no prime factor above 7 is accepted (44 100, 48 000, ...: the mixed-radix four-step
+    kernel of csrc/fft_mixed.hip); the powers of two in [128, 32768] still go to the LDS kernel, bit for bit."""
     if mode not in _MODES:
         raise ValueError(f"Invalid mode {mode}")
-    if fft_size & (fft_size - 1) or not 128 <= fft_size <= 32768:
-        raise NotImplementedError(f"fft_size {fft_size}: only powers of two in [128, 32768] are built")
+    if not _is_lds_size(fft_size):
+        if not mixed_radix:
+            raise NotImplementedError(f"fft_size {fft_size}: only powers of two in [128, 32768] are built")
+        fft_mixed_plan(fft_size)  # NotImplementedError naming the length, before anything touches the GPU
     xin, dev = _gpu(x)
     bs, chs, n = xin.shape
     key = ("fb", fft_size, n_bands, sample_rate, f_min, f_max, str(dev))
@@ -109,8 +160,17 @@ def compute_barkspectrum(x: torch.Tensor, fft_size: int = 32768, n_bands: int = 
     n_sig = 1 if mode == "mono" else 2
     out = torch.empty((bs, n_sig * n_bands), dtype=torch.float32, device=dev)
     L = _hip.lib()
-    _hip.check(L.stito_barkspectrum(_hip.ptr(xin), bs, chs, n, _MODES[mode], fft_size, _hip.ptr(_twiddle(fft_size, dev)),
-                                    _hip.ptr(_cache[key]), n_bands, _hip.ptr(out), _hip.stream_ptr()))
+    if _is_lds_size(fft_size):
+        _hip.check(L.stito_barkspectrum(_hip.ptr(xin), bs, chs, n, _MODES[mode], fft_size, _hip.ptr(_twiddle(fft_size, dev)),
+                                        _hip.ptr(_cache[key]), n_bands, _hip.ptr(out), _hip.stream_ptr()))
+    else:
+        from .engine import _WS
+
+        tables = _mixed_tables(fft_size, dev)
+        ws = _WS.get("bark_mixed", L.stito_barkspectrum_mixed_workspace_bytes(bs, n_sig, fft_size), dev)
+        _hip.check(L.stito_barkspectrum_mixed(_hip.ptr(xin), bs, chs, n, _MODES[mode], fft_size, _hip.ptr(tables), tables.shape[0],
+                                              _hip.ptr(_cache[key]), n_bands, _hip.ptr(out), _hip.ptr(ws), ws.numel(),
+                                              _hip.stream_ptr()))
     return out.to(x.device).type_as(x)
 
 

@@ -196,18 +196,31 @@ def load_mir_feature_extractor(use_gpu: bool = False):
     return Model()
 
 
-def get_mir_feature_embeds(x: torch.Tensor, model, sample_rate: float, **kwargs):
-    """Dictionary of hand-crafted features computed on the GPU (st_ito.features).  The reference
-    (utils.py:76-98) calls compute_barkspectrum(x, sample_rate, mode="mono"), which binds the sample
-    rate to `fft_size` (a 48 000-point FFT at the default 44.1 kHz filterbank); here the arguments
-    are bound as its evaluation wrappers bind them (eval_pst.py:61-69): fft_size 32768 at `sample_rate`."""
+def get_mir_feature_embeds(x: torch.Tensor, model, sample_rate: float, binding: str = "wrappers", **kwargs):
+    """Dictionary of hand-crafted features computed on the GPU (st_ito.features).
+
+    The reference (utils.py:76-98) calls compute_barkspectrum(x, sample_rate, mode="mono").  The second positional
+    parameter of that function is `fft_size`, so the call transforms frames of `sample_rate` samples (48 000 or 44 100
+    points, hop a quarter of that) and leaves the filterbank at its default 44.1 kHz.  Its evaluation wrappers
+    (eval_pst.py:61-69) bind the arguments by name instead: fft_size 32768 at `sample_rate`.  The two give different
+    "barkspectrum" entries, hence two bindings:
+
+      binding="wrappers"   (default) fft_size 32768, filterbank at `sample_rate` -- what this function has always returned;
+      binding="reference"  utils.py:83 literally: compute_barkspectrum(x, fft_size=int(sample_rate), mode="mono") on the
+                           mixed-radix kernel -- the entry the reference's ES optimises when get_mir_feature_embeds is
+                           its embed_func (functools.partial(get_mir_feature_embeds, binding="reference") for run_es).
+
+    The other four entries do not depend on the binding."""
+    if binding not in ("wrappers", "reference"):
+        raise ValueError(f'binding must be "wrappers" or "reference", not {binding!r}')
     from . import features as F
 
+    bark_args = dict(fft_size=int(sample_rate), mixed_radix=True) if binding == "reference" else dict(sample_rate=sample_rate)
     return {
         "lufs": F.compute_lufs(x, sample_rate),
         "rms": F.compute_rms_energy(x),
         "crest": F.compute_crest_factor(x),
-        "barkspectrum": F.compute_barkspectrum(x, sample_rate=sample_rate, mode="mono"),
+        "barkspectrum": F.compute_barkspectrum(x, mode="mono", **bark_args),
         "spectral_centroid": F.compute_spectral_centroid(x, sample_rate),
     }
 
