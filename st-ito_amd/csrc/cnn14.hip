@@ -804,7 +804,10 @@ __global__ __launch_bounds__(256) void k_embed_loss(float *__restrict__ mid, flo
             if (scrub) v = nan_to_num(v);
             ss = fmaf(v, v, ss);
         }
-        const float nrm = fmaxf(sqrtf(block_sum_256(ss, red)), 1e-12f);  // F.normalize eps
+        // F.normalize eps; a NaN norm stays NaN (torch's clamp_min), so an unscrubbed row with a NaN becomes NaN throughout --
+        // fmaxf would drop the NaN and divide the rest of the row by the eps
+        const float nrm0 = sqrtf(block_sum_256(ss, red));
+        const float nrm = nrm0 < 1e-12f ? 1e-12f : nrm0;
         float dot = 0.0f, s2 = 0.0f, t2 = 0.0f;
         for (int i = threadIdx.x; i < E; i += 256) {
             float v = e[i];

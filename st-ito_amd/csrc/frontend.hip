@@ -211,7 +211,8 @@ __global__ __launch_bounds__(FE_THREADS) void k_logmel(FrontendDev fe, const flo
         acc += __shfl_xor(acc, 1);
         acc += __shfl_xor(acc, 2);
         if (!live || part) continue;
-        float v = 10.0f * log10f(fmaxf(acc, 1e-10f));
+        // at the clamp the reference has -100 dB exactly (10 * log10(1e-10) on the host); the device's log10f(1e-10f) is an ulp off
+        float v = acc > 1e-10f ? 10.0f * log10f(acc) : -100.0f;
         if (fe.norm_mode == STITO_NORM_MINMAX) {
             v = fminf(fmaxf(v, -80.0f), 40.0f);
             v = (v + 80.0f) / 120.0f;
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(FE_THREADS, FW_WG_PER_CU) void k_logmel_wave(Fronte
                 acc += __shfl_xor(acc, 1);
                 acc += __shfl_xor(acc, 2);
                 if (!live || part) continue;
-                float v = 10.0f * log10f(fmaxf(acc, 1e-10f));
+                float v = acc > 1e-10f ? 10.0f * log10f(acc) : -100.0f;  // (as k_logmel: -100 dB exactly at the clamp)
                 if (fe.norm_mode == STITO_NORM_MINMAX) {
                     v = fminf(fmaxf(v, -80.0f), 40.0f);
                     v = (v + 80.0f) / 120.0f;
