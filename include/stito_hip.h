@@ -278,7 +278,9 @@ typedef struct {
      * Today: conv_wino_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT3 with conv_alt_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT2 -- the
      * six-sweep kernel's workgroups are four times larger, so a small batch (fewer than 3/4 workgroup per CU) runs the
      * two-sweep kernel instead.  The two kernels do the same arithmetic in the same order: identical bits (tested), so the
-     * choice cannot be seen in the results. */
+     * choice cannot be seen in the results.  conv_alt_dev[i] is consulted on its own: a caller that wants conv i on the direct
+     * kernel clears conv_wino_dev[i] AND conv_alt_dev[i] (with only the first one NULL a small batch still runs the alternative
+     * packing). */
     const float *conv_alt_dev[STITO_CNN14_NUM_CONVS];
     int32_t conv_alt_algo[STITO_CNN14_NUM_CONVS];
     /* ABI v10: depth-first schedule of a run of convs over chunks of streams (replaces the layer-by-layer order of
