@@ -109,7 +109,8 @@ int stito_version(void);
 /* Additions since the last change of stito_version() that leave every existing symbol and struct as it is (a caller built against
  * 10.0 runs unchanged): 1 = stito_gather_crops; 2 = STITO_FX_DASP_EQ, _DASP_COMPRESSOR, _DASP_DISTORTION (kinds 8 - 10 of
  * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits); 3 = stito_barkspectrum_mixed,
- * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan. */
+ * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan; 4 = stito_mrstft_table_floats, stito_mrstft_target,
+ * stito_mrstft_workspace_bytes, stito_mrstft_loss. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -508,6 +509,35 @@ int stito_mfcc_stats(const float *logmel_dev, int n_items, int channels, int64_t
 int stito_gather_crops(const float *packed_dev, int64_t packed_floats, const int64_t *offset_dev, const int64_t *length_dev,
                        const int64_t *start_dev, int n_pairs, const int32_t *slots_dev, int n_slots, int channels,
                        int64_t crop_len, float *out_dev, void *stream);
+
+/* ---- multi-resolution STFT distance as an objective (ABI 10.4; csrc/mrstft.hip) ---------------------------------------------- */
+/* auraloss.freq.MultiResolutionSTFTLoss()(x, y) per item (scripts/eval/eval_synthetic.py:72, 368-369 of the reference; auraloss is
+ * un-vendored: restated, PARITY UNPINNED), x the estimate and y the reference.  res: n_res (1 .. 8) triples (n_fft, hop, win) of
+ * ints, n_fft a power of two in [256, 4096], 1 <= win <= n_fft, hop >= 1; the library's defaults are (1024, 120, 600), (2048, 240,
+ * 1200), (512, 50, 240).  Per row of n_samples > max n_fft / 2 samples and resolution: torch.stft's framing -- reflect padding of
+ * n_fft / 2, frame t = padded samples [t hop, t hop + n_fft), t < 1 + n_samples / hop, the periodic Hann of `win` points at offset
+ * (n_fft - win) / 2, one-sided --, |X| = sqrt(max(re^2 + im^2, 1e-8)), sc = || |Y| - |X| ||_F / || |Y| ||_F, lm = mean |ln|X| - ln|Y||;
+ * an item's loss = the mean over resolutions of the mean over its channel rows of sc + lm.  Not symmetric in x and y.
+ *
+ * stito_mrstft_target: y_dev (rows, n_samples) -> table_dev (stito_mrstft_table_floats floats, 16-byte aligned): the FFT twiddles
+ * and windows of every resolution, per row and resolution the clamped magnitudes (frames x bins, bins contiguous), and sum |Y|^2
+ * per (row, resolution) in float64 (tile sums added in a fixed order; the table holds their scratch too).
+ *
+ * stito_mrstft_loss: audio_dev (pop, channels, n_samples), channels <= 8, scored against a table of n_targets * channels rows built
+ * with the SAME res and n_samples: candidate p against target p / (pop / n_targets), the convention of
+ * stito_render_population_multi.  norm_passes 1 folds x / clip(peaks_dev[p], 1e-8) into the sample loader (stito_logmel's way: the
+ * normalised population is never written); 0: audio as it is, peaks_dev may be NULL.  -> loss_dev (pop) float32.
+ * Each (row, resolution) is cut into tiles of consecutive frames; a tile's sample span is loaded into LDS once, the spectra and the
+ * candidate's magnitudes never leave the CU; per-tile sums (float64) go to the workspace (stito_mrstft_workspace_bytes, 8-byte
+ * aligned) and a second launch adds them in a fixed order: no atomics, and a candidate's loss has the same bits at every position
+ * of every batch, for every n_targets.  The table kernel and the candidate kernel share the FFT and magnitude code, so
+ * loss(y, table(y)) with norm_passes 0 is exactly 0.  The size functions return 0 for arguments the launches refuse. */
+int64_t stito_mrstft_table_floats(const int *res, int n_res, int rows, int64_t n_samples);
+int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev, void *stream);
+size_t stito_mrstft_workspace_bytes(const int *res, int n_res, int pop, int channels, int64_t n_samples);
+int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                      const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
+                      void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

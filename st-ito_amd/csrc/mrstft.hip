@@ -1,0 +1,422 @@
+// mrstft.hip -- multi-resolution STFT distance of a rendered population against target audio, fused.
+//
+// Replaces (reference file:line): auraloss.freq.MultiResolutionSTFTLoss()(x, y) with the library's defaults, the
+// reference's second yardstick -- scripts/eval/eval_synthetic.py:72, 368-369, st_ito/methods/style.py:611 -- as an
+// objective of the ES: per resolution (n_fft, hop, win) and (candidate, channel) row
+//     sc = || |Y| - |X| ||_F / || |Y| ||_F,   lm = mean | ln|X| - ln|Y| |,   |.| = sqrt(max(re^2 + im^2, 1e-8)),
+// torch.stft's framing (centred, reflect padding of n_fft / 2, periodic Hann of `win` points in the middle of the frame,
+// one-sided); an item's loss is the mean over resolutions of the mean over its channels of sc + lm.
+//
+// One workgroup = one tile of F consecutive frames of one (row, resolution).  The tile's sample span (F - 1) hop + n_fft is
+// loaded ONCE into LDS (reflected, with x / clip(peak, 1e-8) folded in like stito_logmel's loader): hop is 8.5 - 10 x smaller
+// than n_fft, so from HBM / L2 every sample is read about once instead of ten times.  Every wave then owns a frame at a
+// time: window, pack the n_fft real samples as n_fft / 2 complex points, an in-place decimation-in-frequency FFT in the
+// wave's own LDS buffer (radix 4, one radix-2 stage last when log2 is odd; the spectrum is left in digit-reversed order
+// and the unpacking reads it there), magnitudes in registers.  Nothing is shared between waves during the frames, and LDS
+// operations of one wave execute in order, so there is no workgroup barrier inside the frame loop.
+//
+// The target's magnitudes come from a table that the same kernel (template TARGET) writes: the FFT and magnitude code is
+// one function compiled without fp contraction (Makefile), so loss(y, table(y)) is exactly 0.  Sums: per lane in float64,
+// per tile a fixed-order tree in LDS, per-tile partials to the workspace, one small launch adds the tiles in order -- no
+// atomics, and a candidate's loss depends on nothing but its own audio, its target and the resolutions.
+#include "common.h"
+
+namespace stito {
+
+static constexpr int MR_THREADS = 256, MR_WAVES = MR_THREADS / 64;
+static constexpr int MR_MAX_RES = 8;
+static constexpr int MR_MAX_CH = 8;  // the final sum gives one lane of a wave to every (resolution, channel)
+
+// Everything the launches of one (resolutions, n) need, worked out once on the host: frames, tiles, LDS, and where the
+// pieces of the table and of the workspace lie.  Table (floats; every offset even, so doubles and float2 are aligned):
+//   per resolution   n_fft / 2 float2 exp(-2 pi i t / n_fft), then the n_fft window values          at hdr_off[i]
+//   per row          per resolution frames x bins magnitudes, bins contiguous                       at mags_base + row * row_floats + mag_off[i]
+//   rows x n_res     doubles: sum |Y|^2                                                             at mags_base + rows * row_floats
+//   rows x tiles_total doubles: its per-tile partial sums (scratch of stito_mrstft_target)          behind them
+struct MrPlan {
+    int n_res;
+    int nfft[MR_MAX_RES], hop[MR_MAX_RES], win[MR_MAX_RES], log2_n2[MR_MAX_RES], F[MR_MAX_RES];
+    int64_t T[MR_MAX_RES], tiles[MR_MAX_RES], bins[MR_MAX_RES];
+    size_t lds[MR_MAX_RES];
+    int64_t hdr_off[MR_MAX_RES], mag_off[MR_MAX_RES], tile_off[MR_MAX_RES];
+    int64_t row_floats, mags_base, tiles_total;
+};
+
+static size_t mr_lds_bytes(int N, int hop, int F) {
+    // tile sums (2 x MR_THREADS doubles) + one FFT buffer per wave + twiddles + window + sample span
+    return (size_t)2 * MR_THREADS * 8 + (size_t)MR_WAVES * (N / 2) * 8 + (size_t)(N / 2) * 8 + (size_t)N * 4 +
+           ((size_t)(F - 1) * hop + N) * 4;
+}
+
+static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p) {
+    STITO_REQUIRE(res != nullptr, STITO_E_INVALID, "mrstft: null resolutions");
+    STITO_REQUIRE(n_res >= 1 && n_res <= MR_MAX_RES, STITO_E_INVALID, "mrstft: %d resolutions, 1 .. %d are supported", n_res, MR_MAX_RES);
+    // gfx950's LDS per workgroup: the plan also sizes the table and the workspace, so it asks no device (mr_device_fits does)
+    const size_t lds_cap = 160 * 1024;
+    p.n_res = n_res;
+    int64_t hdr = 0, mag = 0, tl = 0;
+    for (int i = 0; i < n_res; ++i) {
+        const int N = res[3 * i], hop = res[3 * i + 1], win = res[3 * i + 2];
+        STITO_REQUIRE(N >= 256 && N <= 4096 && (N & (N - 1)) == 0, STITO_E_INVALID, "mrstft: n_fft %d must be a power of two in [256, 4096]", N);
+        STITO_REQUIRE(hop >= 1, STITO_E_INVALID, "mrstft: hop %d must be at least 1", hop);
+        STITO_REQUIRE(win >= 1 && win <= N, STITO_E_INVALID, "mrstft: window of %d points does not fit n_fft %d", win, N);
+        STITO_REQUIRE(n > N / 2, STITO_E_INVALID, "mrstft: %lld samples are too few for the reflect padding of n_fft %d", (long long)n, N);
+        STITO_REQUIRE(n < ((int64_t)1 << 40), STITO_E_INVALID, "mrstft: %lld samples", (long long)n);
+        p.nfft[i] = N; p.hop[i] = hop; p.win[i] = win;
+        int l2 = 0;
+        while ((1 << l2) < N / 2) ++l2;
+        p.log2_n2[i] = l2;
+        p.T[i] = 1 + n / hop;
+        p.bins[i] = N / 2 + 1;
+        // frames per tile: as many as 32 while two workgroups fit a CU's 160 KB of LDS, else what one workgroup can hold
+        static const int cand_F[] = {32, 28, 24, 20, 16, 12, 8, 4, 2, 1};
+        int F = 0;
+        for (size_t budget : {(size_t)80 * 1024, lds_cap}) {
+            for (int f : cand_F)
+                if (mr_lds_bytes(N, hop, f) <= budget && mr_lds_bytes(N, hop, f) <= lds_cap) { F = f; break; }
+            if (F) break;
+        }
+        STITO_REQUIRE(F > 0, STITO_E_UNSUPPORTED, "mrstft: n_fft %d needs %zu bytes of LDS per workgroup, the device has %zu", N,
+                      mr_lds_bytes(N, hop, 1), lds_cap);
+        p.F[i] = F;
+        p.lds[i] = mr_lds_bytes(N, hop, F);
+        p.tiles[i] = (p.T[i] + F - 1) / F;
+        p.hdr_off[i] = hdr; hdr += 2 * (int64_t)N;
+        p.mag_off[i] = mag; mag += (p.T[i] * p.bins[i] + 1) / 2 * 2;
+        p.tile_off[i] = tl; tl += p.tiles[i];
+    }
+    p.mags_base = hdr; p.row_floats = mag; p.tiles_total = tl;
+    return STITO_OK;
+}
+
+static int mr_device_fits(const MrPlan &p) {
+    DeviceInfo di;
+    STITO_TRY(device_info(di));
+    for (int i = 0; i < p.n_res; ++i)
+        STITO_REQUIRE(p.lds[i] <= (size_t)di.lds_per_block, STITO_E_UNSUPPORTED, "mrstft: n_fft %d needs %zu bytes of LDS per workgroup, the device has %d",
+                      p.nfft[i], p.lds[i], di.lds_per_block);
+    return STITO_OK;
+}
+
+static int64_t mr_table_floats(const MrPlan &p, int64_t rows) {
+    return p.mags_base + rows * p.row_floats + 2 * rows * p.n_res + 2 * rows * p.tiles_total;
+}
+
+struct MrDev {
+    int N, N2, log2_n2, hop, F, tiles;
+    int64_t T, bins, n;
+    const float2 *tw;     // exp(-2 pi i t / N), t < N2
+    const float *win;     // N window values (zero outside the Hann of `win` points)
+    float *mags;          // the table's row blocks + this resolution's offset; row stride row_floats
+    int64_t row_floats;
+    double *partial;      // [row][tiles_total][K] + this resolution's tile offset * K
+    int64_t tiles_total;
+};
+
+__device__ __forceinline__ float2 mr_cmul(float2 a, float2 b) {  // explicit fmas: the file is built with -ffp-contract=off
+    return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
+}
+__device__ __forceinline__ float2 mr_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 mr_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// LDS operations of one wave execute in order; this keeps the compiler from moving them and waits for the reads
+#define MR_WAVE_SYNC() { __builtin_amdgcn_wave_barrier(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+
+// Position in the wave's buffer of bin k of the N2-point transform after the in-place stages: stage s of radix r_s sends
+// the bins with k mod r_s = d to sub-block d, so the digits of k (least significant first) become those of the position
+// (most significant first).  Radix-4 stages, then one radix-2 stage when log2(N2) is odd.
+__device__ __forceinline__ int mr_pos(int k, int log2_n2) {
+    const int even = log2_n2 & ~1;
+    unsigned v = __brev((unsigned)k & ((1u << even) - 1u)) >> (32 - even);   // bits reversed: digits reversed, each digit's two bits too
+    v = ((v & 0x55555555u) << 1) | ((v >> 1) & 0x55555555u);
+    return (log2_n2 & 1) ? (int)((v << 1) | ((unsigned)k >> even)) : (int)v;
+}
+
+// One frame: samples sp[0 .. N) of the tile's span -> window -> packed complex FFT in buf.  All lanes of the wave.
+__device__ __forceinline__ void mr_frame_fft(const MrDev &d, const float *sp, const float *win_s, const float2 *tw_s, float2 *buf, int lane) {
+    const int N2 = d.N2;
+    for (int m = lane; m < N2; m += 64)
+        buf[m] = make_float2(sp[2 * m] * win_s[2 * m], sp[2 * m + 1] * win_s[2 * m + 1]);
+    MR_WAVE_SYNC()
+    int lm = d.log2_n2;                       // log2 of the current block size
+    for (; lm >= 2; lm -= 2) {
+        const int q = 1 << (lm - 2);          // quarter of the block
+        const int sh = d.log2_n2 + 1 - lm;    // exp(-2 pi i j / block) = tw[j << sh]
+        for (int i = lane; i < (N2 >> 2); i += 64) {
+            const int j = i & (q - 1);
+            const int base = ((i >> (lm - 2)) << lm) + j;
+            const float2 w1 = tw_s[j << sh], w2 = tw_s[(2 * j) << sh];
+            const float2 w3 = mr_cmul(w1, w2);
+            const float2 a0 = buf[base], a1 = buf[base + q], a2 = buf[base + 2 * q], a3 = buf[base + 3 * q];
+            const float2 b0 = mr_add(a0, a2), b1 = mr_sub(a0, a2), b2 = mr_add(a1, a3), b3 = mr_sub(a1, a3);
+            buf[base] = mr_add(b0, b2);
+            buf[base + q] = mr_cmul(make_float2(b1.x + b3.y, b1.y - b3.x), w1);      // (b1 - i b3) w
+            buf[base + 2 * q] = mr_cmul(mr_sub(b0, b2), w2);
+            buf[base + 3 * q] = mr_cmul(make_float2(b1.x - b3.y, b1.y + b3.x), w3);  // (b1 + i b3) w^3
+        }
+        MR_WAVE_SYNC()
+    }
+    if (lm == 1) {
+        for (int i = lane; i < (N2 >> 1); i += 64) {
+            const float2 a0 = buf[2 * i], a1 = buf[2 * i + 1];
+            buf[2 * i] = mr_add(a0, a1);
+            buf[2 * i + 1] = mr_sub(a0, a1);
+        }
+        MR_WAVE_SYNC()
+    }
+}
+
+// |X[k]| of the real frame from the packed transform Z (digit-reversed in buf): X[k] = E[k] + W^k O[k], clamped like the reference
+__device__ __forceinline__ float mr_magnitude(const MrDev &d, const float2 *buf, const float2 *tw_s, int k) {
+    const int N2 = d.N2;
+    const float2 zk = buf[mr_pos(k & (N2 - 1), d.log2_n2)];
+    const float2 zn = buf[mr_pos((N2 - k) & (N2 - 1), d.log2_n2)];
+    const float2 E = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
+    const float2 O = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));  // (zk - conj(zn)) / (2i)
+    const float2 w = (k < N2) ? tw_s[k] : make_float2(-1.0f, 0.0f);
+    const float2 wo = mr_cmul(w, O);
+    const float re = E.x + wo.x, im = E.y + wo.y;
+    return sqrtf(fmaxf(fmaf(re, re, im * im), 1e-8f));
+}
+
+// TARGET: audio = y (rows, n); writes the magnitudes and the tile's sum |Y|^2 (K = 1 partial).
+// else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row (cand / per_target) * C + ch;
+//         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).
+template <bool TARGET>
+__global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__restrict__ audio, const float *__restrict__ peaks,
+                                                      int norm_passes, int C, int per_target) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int N = d.N, N2 = d.N2;
+    double *red = (double *)smem_raw;                          // [2][MR_THREADS]
+    float2 *bufs = (float2 *)(red + 2 * MR_THREADS);           // [MR_WAVES][N2]
+    float2 *tw_s = bufs + MR_WAVES * N2;                       // [N2]
+    float *win_s = (float *)(tw_s + N2);                       // [N]
+    float *span = win_s + N;                                   // [(F - 1) hop + N]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t row = blockIdx.x / d.tiles;
+    const int tile = (int)(blockIdx.x - row * d.tiles);
+    const int64_t t0 = (int64_t)tile * d.F;
+    const int nf = (int)(d.T - t0 < d.F ? d.T - t0 : d.F);
+
+    float r1 = 1.0f;
+    int64_t trow = row;
+    if (!TARGET) {
+        const int64_t cand = row / C;
+        if (peaks != nullptr && norm_passes > 0) r1 = 1.0f / fmaxf(peaks[cand], 1e-8f);  // x * (1 / d), as stito_logmel
+        trow = (cand / per_target) * C + (row - cand * C);
+    }
+    const float *x = audio + row * d.n;
+
+    for (int i = tid; i < N2; i += MR_THREADS) tw_s[i] = d.tw[i];
+    for (int i = tid; i < N; i += MR_THREADS) win_s[i] = d.win[i];
+    // the span: padded samples [t0 hop, t0 hop + (nf - 1) hop + N), padded index i = sample i - N / 2, reflected (no edge repeat)
+    const int span_len = (nf - 1) * d.hop + N;
+    const int64_t s0 = t0 * d.hop - N2;
+    for (int i = tid; i < span_len; i += MR_THREADS) {
+        int64_t s = s0 + i;
+        if (s < 0) s = -s;
+        if (s >= d.n) s = 2 * (d.n - 1) - s;
+        span[i] = x[s] * r1;
+    }
+    __syncthreads();
+
+    double acc0 = 0.0, acc1 = 0.0;
+    float2 *buf = bufs + wave * N2;
+    float *mags = d.mags + trow * d.row_floats;
+    for (int f = wave; f < nf; f += MR_WAVES) {
+        mr_frame_fft(d, span + f * d.hop, win_s, tw_s, buf, lane);
+        float *mrow = mags + (t0 + f) * d.bins;
+        for (int k = lane; k <= N2; k += 64) {
+            const float mx = mr_magnitude(d, buf, tw_s, k);
+            if (TARGET) {
+                mrow[k] = mx;
+                acc0 += (double)(mx * mx);
+            } else {
+                const float my = mrow[k];
+                const float df = my - mx;
+                acc0 += (double)(df * df);
+                acc1 += (double)fabsf(logf(mx / my));
+            }
+        }
+        MR_WAVE_SYNC()  // the spectrum has been read before the next frame is packed over it
+    }
+
+    // the tile's sums: a fixed tree over the threads
+    red[tid] = acc0;
+    red[MR_THREADS + tid] = acc1;
+    __syncthreads();
+    for (int s = MR_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            red[tid] += red[tid + s];
+            red[MR_THREADS + tid] += red[MR_THREADS + tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        constexpr int K = TARGET ? 1 : 2;
+        double *out = d.partial + (row * d.tiles_total + tile) * K;
+        out[0] = red[0];
+        if (!TARGET) out[1] = red[MR_THREADS];
+    }
+}
+
+// exp(-2 pi i t / N), t < N / 2, and the periodic Hann of `win` points in the middle of N: float64, rounded once
+__global__ void k_mrstft_tables(float2 *tw, float *window, int N, int win) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N / 2) {
+        double s, c;
+        sincospi(-2.0 * (double)i / (double)N, &s, &c);
+        tw[i] = make_float2((float)c, (float)s);
+    }
+    if (i < N) {
+        const int lo = (N - win) / 2, k = i - lo;
+        window[i] = (k >= 0 && k < win) ? (float)(0.5 - 0.5 * cospi(2.0 * (double)k / (double)win)) : 0.0f;
+    }
+}
+
+struct MrSum {
+    int n_res;
+    int tiles[MR_MAX_RES], tile_off[MR_MAX_RES];
+    double count[MR_MAX_RES];  // frames x bins
+    int64_t tiles_total;
+};
+
+// sum |Y|^2 per (row, resolution): the tiles in order
+__global__ void k_mrstft_target_sum(MrSum s, const double *__restrict__ partial, int64_t rows, double *__restrict__ sums) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * s.n_res) return;
+    const int64_t row = i / s.n_res;
+    const int r = (int)(i - row * s.n_res);
+    const double *p = partial + row * s.tiles_total + s.tile_off[r];
+    double acc = 0.0;
+    for (int t = 0; t < s.tiles[r]; ++t) acc += p[t];
+    sums[i] = acc;
+}
+
+// one wave per candidate: lane (resolution, channel) adds its tiles in order, lane 0 the means in order
+__global__ __launch_bounds__(64) void k_mrstft_final(MrSum s, const double *__restrict__ partial, const double *__restrict__ ysum, int C,
+                                                     int per_target, float *__restrict__ loss) {
+    __shared__ double term[64];
+    const int cand = blockIdx.x, lane = threadIdx.x;
+    if (lane < s.n_res * C) {
+        const int r = lane / C, ch = lane - r * C;
+        const int64_t row = (int64_t)cand * C + ch, trow = (int64_t)(cand / per_target) * C + ch;
+        const double *p = partial + (row * s.tiles_total + s.tile_off[r]) * 2;
+        double d2 = 0.0, lg = 0.0;
+        for (int t = 0; t < s.tiles[r]; ++t) { d2 += p[2 * t]; lg += p[2 * t + 1]; }
+        term[lane] = sqrt(d2) / sqrt(ysum[trow * s.n_res + r]) + lg / s.count[r];
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double total = 0.0;
+        for (int r = 0; r < s.n_res; ++r) {
+            double acc = 0.0;
+            for (int ch = 0; ch < C; ++ch) acc += term[r * C + ch];
+            total += acc / C;
+        }
+        loss[cand] = (float)(total / s.n_res);
+    }
+}
+
+static MrDev mr_dev(const MrPlan &p, int i, int64_t n, float *table, double *partial, int K) {
+    MrDev d;
+    d.N = p.nfft[i]; d.N2 = d.N / 2; d.log2_n2 = p.log2_n2[i]; d.hop = p.hop[i]; d.F = p.F[i]; d.tiles = (int)p.tiles[i];
+    d.T = p.T[i]; d.bins = p.bins[i]; d.n = n;
+    d.tw = (const float2 *)(table + p.hdr_off[i]);
+    d.win = table + p.hdr_off[i] + d.N;
+    d.mags = table + p.mags_base + p.mag_off[i];
+    d.row_floats = p.row_floats;
+    d.partial = partial + p.tile_off[i] * K;
+    d.tiles_total = p.tiles_total;
+    return d;
+}
+
+static MrSum mr_sum(const MrPlan &p) {
+    MrSum s;
+    s.n_res = p.n_res; s.tiles_total = p.tiles_total;
+    for (int i = 0; i < MR_MAX_RES; ++i) {
+        const bool live = i < p.n_res;
+        s.tiles[i] = live ? (int)p.tiles[i] : 0;
+        s.tile_off[i] = live ? (int)p.tile_off[i] : 0;
+        s.count[i] = live ? (double)p.T[i] * (double)p.bins[i] : 1.0;
+    }
+    return s;
+}
+
+}  // namespace stito
+
+using namespace stito;
+
+extern "C" int64_t stito_mrstft_table_floats(const int *res, int n_res, int rows, int64_t n_samples) {
+    MrPlan p;
+    if (rows < 1 || mr_plan(res, n_res, n_samples, p) != STITO_OK) return 0;
+    return mr_table_floats(p, rows);
+}
+
+extern "C" size_t stito_mrstft_workspace_bytes(const int *res, int n_res, int pop, int channels, int64_t n_samples) {
+    MrPlan p;
+    if (pop < 1 || channels < 1 || mr_plan(res, n_res, n_samples, p) != STITO_OK) return 0;
+    return (size_t)pop * channels * p.tiles_total * 2 * sizeof(double);
+}
+
+extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
+                                   void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    MrPlan p;
+    STITO_TRY(mr_plan(res, n_res, n_samples, p));
+    STITO_TRY(mr_device_fits(p));
+    STITO_REQUIRE(rows >= 1, STITO_E_INVALID, "stito_mrstft_target: %d rows", rows);
+    STITO_REQUIRE(y_dev != nullptr && table_dev != nullptr, STITO_E_INVALID, "stito_mrstft_target: null pointer");
+    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "stito_mrstft_target: the table must be 16-byte aligned");
+    double *sums = (double *)(table_dev + p.mags_base + (int64_t)rows * p.row_floats);
+    double *partial = sums + (int64_t)rows * p.n_res;
+    for (int i = 0; i < p.n_res; ++i) {
+        STITO_REQUIRE((int64_t)rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "stito_mrstft_target: too many tiles");
+        const MrDev d = mr_dev(p, i, n_samples, table_dev, partial, 1);
+        hipLaunchKernelGGL(k_mrstft_tables, dim3((d.N + 255) / 256), dim3(256), 0, st, (float2 *)d.tw, (float *)d.win, d.N, p.win[i]);
+        STITO_LAUNCH_CHECK();
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL(k_mrstft<true>, dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
+                           (const float *)nullptr, 0, 1, 1);
+        STITO_LAUNCH_CHECK();
+    }
+    const int64_t n_sums = (int64_t)rows * p.n_res;
+    hipLaunchKernelGGL(k_mrstft_target_sum, dim3((unsigned)((n_sums + 63) / 64)), dim3(64), 0, st, mr_sum(p), partial, (int64_t)rows, sums);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}
+
+extern "C" int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                                 const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
+                                 void *workspace_dev, size_t workspace_bytes, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    MrPlan p;
+    STITO_TRY(mr_plan(res, n_res, n_samples, p));
+    STITO_TRY(mr_device_fits(p));
+    STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "stito_mrstft_loss: pop %d, n_targets %d", pop, n_targets);
+    STITO_REQUIRE(pop % n_targets == 0, STITO_E_INVALID, "stito_mrstft_loss: population %d is not a multiple of the number of targets %d", pop, n_targets);
+    STITO_REQUIRE(channels >= 1 && channels <= MR_MAX_CH && n_res * channels <= 64, STITO_E_INVALID, "Invalid number of channels: %d", channels);
+    STITO_REQUIRE(norm_passes == 0 || norm_passes == 1, STITO_E_INVALID, "stito_mrstft_loss: norm_passes %d must be 0 or 1", norm_passes);
+    STITO_REQUIRE(norm_passes == 0 || peaks_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss: norm_passes 1 needs the peaks");
+    STITO_REQUIRE(audio_dev != nullptr && table_dev != nullptr && loss_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss: null pointer");
+    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "stito_mrstft_loss: the table must be 16-byte aligned");
+    const int64_t rows = (int64_t)pop * channels, trows = (int64_t)n_targets * channels;
+    const size_t need = (size_t)rows * p.tiles_total * 2 * sizeof(double);
+    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= need, STITO_E_WORKSPACE, "stito_mrstft_loss: workspace of %zu bytes, %zu needed",
+                  workspace_bytes, need);
+    STITO_REQUIRE(((uintptr_t)workspace_dev & 7) == 0, STITO_E_INVALID, "stito_mrstft_loss: the workspace must be 8-byte aligned");
+    double *partial = (double *)workspace_dev;
+    const double *ysum = (const double *)(table_dev + p.mags_base + trows * p.row_floats);
+    for (int i = 0; i < p.n_res; ++i) {
+        STITO_REQUIRE(rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "stito_mrstft_loss: too many tiles");
+        const MrDev d = mr_dev(p, i, n_samples, (float *)table_dev, partial, 2);
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL(k_mrstft<false>, dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev, peaks_dev,
+                           norm_passes, channels, pop / n_targets);
+        STITO_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_mrstft_final, dim3((unsigned)pop), dim3(64), 0, st, mr_sum(p), partial, ysum, channels, pop / n_targets, loss_dev);
+    STITO_LAUNCH_CHECK();
+    return STITO_OK;
+}

@@ -51,6 +51,9 @@ def build_parser():
     parser.add_argument("--no-early-stop", action="store_true")
     parser.add_argument("--no-find-w0", action="store_true")
     parser.add_argument("--output-dir", type=str, default="output/optim")
+    parser.add_argument("--objective", type=str, default="embedding", choices=["embedding", "mrstft"],
+                        help="embedding: cosine distance of the --metric embeddings (the reference); mrstft: multi-resolution STFT "
+                             "distance to the target audio itself (same length as the input; no checkpoint is loaded)")
     return parser
 
 
@@ -106,11 +109,13 @@ def main(argv=None):
     run_dir = os.path.join(args.output_dir, run_name)
     os.makedirs(run_dir, exist_ok=True)
 
-    if args.synthetic:
-        model = make_synthetic_param_model(seed=0)
+    if args.objective == "mrstft":
+        if args.staged:
+            raise NotImplementedError("--objective mrstft is built for run_es only, not --staged")
+        model, embed_func = None, None  # the distance is taken on the audio: no checkpoint
     else:
-        model = load_param_model(ckpt_path=args.ckpt, use_gpu=args.use_gpu)
-    embed_func = get_param_embeds
+        model = make_synthetic_param_model(seed=0) if args.synthetic else load_param_model(ckpt_path=args.ckpt, use_gpu=args.use_gpu)
+        embed_func = get_param_embeds
 
     if rank == 0:
         save_wav(os.path.join(run_dir, "input_audio.wav"), input_audio, sample_rate)
@@ -124,7 +129,7 @@ def main(argv=None):
     result = es_func(
         input_audio.unsqueeze(0), target_audio.unsqueeze(0), sample_rate, plugins, model, embed_func,
         max_iters=args.max_iters, popsize=args.popsize, w0=w0, find_w0=not args.no_find_w0, sigma0=sigma0,
-        distance="cosine", parallel=args.parallel, dropout=args.dropout, savepop=args.savepop,
+        distance="mrstft" if args.objective == "mrstft" else "cosine", parallel=args.parallel, dropout=args.dropout, savepop=args.savepop,
         normalize_stages=args.normalize_stages, run_dir=run_dir, seed=args.seed,
         early_stop=not args.no_early_stop,
     )

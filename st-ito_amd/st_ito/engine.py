@@ -165,6 +165,16 @@ def compile_chain(plugins: Dict[str, dict], normalize_stages: bool = False) -> T
     return descs, off
 
 
+def chain_out_channels(plugins: Dict[str, dict], in_channels: int) -> int:
+    """Channels of the rendered audio (style_transfer.py:94-104; stito_chain_out_channels on the host, before a chain is
+    compiled): a 2-channel plugin up-mixes a mono signal, except the dasp compressor, which never does."""
+    c = int(in_channels)
+    for plugin in plugins.values():
+        if int(plugin["num_channels"]) == 2 and c == 1 and getattr(_instance_of(plugin), "KIND", -1) != _hip.FX_DASP_COMPRESSOR:
+            c = 2
+    return c
+
+
 class _Workspace:
     """Grow-only device scratch buffers keyed by name (torch owns the memory)."""
 
@@ -565,4 +575,91 @@ class PopulationEvaluator:
             return "Warning: NaNs found in mid_embeddings"
         if fl.numel() and int(fl[1]):
             return "Warning: NaNs found in side_embeddings"
+        return None
+
+
+class MrstftEvaluator:
+    """The evaluate step with the multi-resolution STFT distance to the target AUDIO as the objective (auraloss's
+    MultiResolutionSTFTLoss, the reference's second yardstick: scripts/eval/eval_synthetic.py:72, 368-369): render ->
+    stito_mrstft_loss with process_audio's joint peak normalisation folded into the kernel's loader.  No model, no embeddings.
+
+    x (B, C, n) and target_audio (B, C', n), C' the chain's output channels: candidates of pair b are scored against target b
+    (evaluate takes the B populations stacked pair-major, like PopulationEvaluator).  The length policy is the embedding
+    objective's (style_transfer.py:505-518) and the target receives the same span: the same zero padding to 262144, the same
+    crop, and under random_crop the same start -- its table is rebuilt for that crop, one launch sequence on its C' rows.
+    Launches are eager."""
+
+    def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor,
+                 device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False):
+        from . import features as _features
+
+        if x.dim() != 3 or target_audio.dim() != 3:
+            raise ValueError("input and target audio must be (batch, chs, seq_len)")
+        if target_audio.shape[0] != x.shape[0] or target_audio.shape[-1] != x.shape[-1]:
+            raise ValueError(f"target audio {tuple(target_audio.shape)} does not cover the input {tuple(x.shape)}: the MRSTFT "
+                             "objective compares sample spans, so batch and length must be equal")
+        _features._mrstft_res(resolutions)
+        _hip.require_gpu()
+        self.device = device or _current_device()
+        self.sample_rate = sample_rate
+        self.plugins = plugins
+        self.resolutions = resolutions
+        self.chain = compile_chain(plugins, normalize_stages)
+        self.ndims = self.chain[1]
+        self.n_inputs = x.shape[0]
+        c_out = _hip.lib().stito_chain_out_channels(self.chain[0], len(plugins), x.shape[1])
+        if target_audio.shape[1] != c_out:
+            raise ValueError(f"target audio has {target_audio.shape[1]} channels, the chain renders {c_out}")
+        self.x_full = x.to(self.device, torch.float32).contiguous()
+        self.y_full = target_audio.to(self.device, torch.float32).contiguous()
+        self._padded = None    # (x, y) zero padded to 262144, built once
+        self._targets = {}     # evaluate-time length -> MrstftTarget (its table is refilled when the span moves)
+        self._table_span = {}  # evaluate-time length -> the span the table currently holds
+        self.rendered_candidates = 0
+
+    def _spans(self, random_crop: bool, rng, parallel: bool):
+        """-> (x, y, key of the span): PopulationEvaluator._input's policy applied to input and target alike."""
+        x, y = self.x_full, self.y_full
+        n = x.shape[-1]
+        if parallel:
+            return x, y, ("full",)
+        start, length = crop_start(n, random_crop, rng), eval_length(n, random_crop)
+        if length == n:
+            return x, y, ("full",)
+        if length < n:
+            return x[..., start:start + length].contiguous(), y[..., start:start + length].contiguous(), ("crop", start)
+        if self._padded is None:
+            pad = lambda t: torch.nn.functional.pad(t, (0, length - n)).contiguous()  # noqa: E731
+            self._padded = (pad(x), pad(y))
+        return (*self._padded, ("pad",))
+
+    def evaluate(self, W, random_crop: bool = False, rng=np.random, want_audio: bool = False, dropout: float = 0.0,
+                 parallel: bool = False):
+        """Fitness of every row of W -> (loss (P,), {}, normalised audio or None)."""
+        from . import features as _features
+
+        if dropout > 0.0:
+            raise ValueError("dropout acts on embeddings; the MRSTFT objective has none")
+        Wn = np.asarray(W, dtype=np.float64)
+        if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
+            raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
+        P = Wn.shape[0]
+        if P == 0 or P % self.n_inputs:
+            raise ValueError(f"{P} candidates cannot be split over {self.n_inputs} inputs")
+        x, y, span = self._spans(random_crop, rng, parallel)
+        length = x.shape[-1]
+        tgt = self._targets.get(length)
+        if tgt is None:
+            tgt = self._targets[length] = _features.MrstftTarget(y, self.resolutions)
+        elif self._table_span[length] != span:
+            tgt.update(y)
+        self._table_span[length] = span
+        Wt = torch.from_numpy(Wn).to(self.device)
+        xin = x[0] if x.shape[0] == 1 else x
+        audio, peaks = render_population(self.plugins, xin, Wt, self.sample_rate, chain=self.chain)
+        self.rendered_candidates += P
+        loss = tgt.loss(audio, peaks, norm_passes=1)
+        return loss, {}, (normalize_audio_(audio, peaks) if want_audio else None)
+
+    def nan_warning(self) -> Optional[str]:
         return None

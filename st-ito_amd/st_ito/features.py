@@ -247,3 +247,94 @@ def compute_spectral_centroid(x: torch.Tensor, sample_rate: float, *args, **kwar
     _hip.check(L.stito_spectral_centroid(_hip.ptr(xin), bs, chs, n, float(sample_rate), _hip.ptr(_cache[key]),
                                          _hip.ptr(_twiddle(2048, dev)), _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
     return out.to(x.device).type_as(x)
+
+
+# --------------------------------------------------------------------------------------------
+# multi-resolution STFT distance (csrc/mrstft.hip)
+# --------------------------------------------------------------------------------------------
+MRSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))  # auraloss's defaults: (n_fft, hop, win)
+
+
+def _mrstft_res(resolutions):
+    """(ctypes int array of the (n_fft, hop, win) triples, their number); ValueError for what the kernel cannot take."""
+    import ctypes
+
+    res = [tuple(int(v) for v in r) for r in (MRSTFT_RESOLUTIONS if resolutions is None else resolutions)]
+    if not 1 <= len(res) <= 8 or any(len(r) != 3 for r in res):
+        raise ValueError("resolutions must be 1 .. 8 triples (n_fft, hop, win)")
+    for n_fft, hop, win in res:
+        if n_fft < 256 or n_fft > 4096 or n_fft & (n_fft - 1):
+            raise ValueError(f"n_fft {n_fft} must be a power of two in [256, 4096]")
+        if hop < 1 or not 1 <= win <= n_fft:
+            raise ValueError(f"hop {hop} / win {win} do not fit n_fft {n_fft}")
+    flat = [v for r in res for v in r]
+    return (ctypes.c_int * len(flat))(*flat), len(res)
+
+
+def _mrstft_check_length(n: int, resolutions) -> None:
+    """torch.stft's condition for reflect padding: more samples than half the largest n_fft."""
+    res = MRSTFT_RESOLUTIONS if resolutions is None else resolutions
+    half = max(int(r[0]) for r in res) // 2
+    if int(n) <= half:
+        raise ValueError(f"{int(n)} samples are too few for the reflect padding of n_fft {2 * half} (more than {half} are needed)")
+
+
+class MrstftTarget:
+    """The target side of the distance on the device: the table stito_mrstft_target writes for y (T, C, n) -- FFT tables,
+    clamped magnitudes per (row, resolution), sum |Y|^2 -- in a buffer that `update` refills for another y of the same shape."""
+
+    def __init__(self, y: torch.Tensor, resolutions=None):
+        self.res, self.n_res = _mrstft_res(resolutions)
+        if y.dim() != 3:
+            raise ValueError("expected (n_targets, chs, seq_len)")
+        _mrstft_check_length(y.shape[-1], resolutions)
+        self.resolutions = resolutions
+        self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
+        floats = _hip.lib().stito_mrstft_table_floats(self.res, self.n_res, self.n_targets * self.channels, self.n)
+        if floats <= 0:
+            raise ValueError(f"no MRSTFT table for {tuple(y.shape)} audio")
+        self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
+        self.update(y)
+
+    def update(self, y: torch.Tensor) -> "MrstftTarget":
+        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
+        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
+            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
+        y = y.contiguous()
+        _hip.check(_hip.lib().stito_mrstft_target(self.res, self.n_res, _hip.ptr(y), self.n_targets * self.channels, self.n,
+                                                  _hip.ptr(self.table), _hip.stream_ptr()))
+        return self
+
+    def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0) -> torch.Tensor:
+        """audio (P, C, n) float32 on the GPU, P a multiple of the number of targets (candidate p against target p // (P // T))
+        -> (P,) float32.  norm_passes 1: audio[p] / clip(peaks[p], 1e-8) is what gets scored, folded into the kernel's loader."""
+        from .engine import _WS
+
+        if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
+            raise ValueError(f"audio must be (P, {self.channels}, {self.n}), got {tuple(audio.shape)}")
+        assert audio.is_cuda and audio.dtype == torch.float32
+        audio = audio.contiguous()
+        P = audio.shape[0]
+        L = _hip.lib()
+        ws = _WS.get("mrstft", L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device)
+        out = torch.empty(P, dtype=torch.float32, device=audio.device)
+        _hip.check(L.stito_mrstft_loss(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+                                       self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(),
+                                       _hip.stream_ptr()))
+        return out
+
+
+def compute_mrstft_distance(x: torch.Tensor, y: torch.Tensor, resolutions=None) -> torch.Tensor:
+    """auraloss.freq.MultiResolutionSTFTLoss()(x[b], y[b]) per item -> (B,) float32 on x's device (the library's batch value is
+    the mean of these); x (B, C, n) the estimate, y (B, C, n) or (1, C, n) the reference.  resolutions: triples (n_fft, hop,
+    win), default auraloss's (1024, 120, 600), (2048, 240, 1200), (512, 50, 240).  One fused kernel per resolution
+    (stito_mrstft_loss): the spectra never reach HBM."""
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("expected (bs, chs, seq_len)")
+    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _mrstft_res(resolutions)
+    _mrstft_check_length(x.shape[-1], resolutions)
+    xin, dev = _gpu(x)
+    yin = y.detach().to(dev, torch.float32).contiguous()
+    return MrstftTarget(yin, resolutions).loss(xin).to(x.device)

@@ -400,18 +400,26 @@ def run_es(
     reference is unseeded) and `early_stop` (False disables the break of lines 655-670 for fixed
     work benchmarks).  Under torch.distributed each rank evaluates a contiguous shard of the
     population and the fitness scalars are all-gathered; the CMA-ES state is replicated."""
-    if distance != "cosine":
+    if distance not in ("cosine", "mrstft"):
         raise ValueError(f"Unknown distance: {distance}")
     if content_model is not None and content_embed_func is None:
         raise ValueError("content_model needs a content_embed_func")
     bs, chs, seq_len = input_audio.shape
-    _, rank, world = _dist_info()
+    if distance == "mrstft":
+        _check_mrstft_run(input_audio, target_audio, plugins, content_model, dropout, savepop)
     seed = _agree_on_seed(seed)
     rng = np.random.RandomState(seed) if seed is not None else np.random
 
     # peak normalize (in place like the reference, 452-453)
     _peak_normalize_(input_audio)
     _peak_normalize_(target_audio)
+
+    if distance == "mrstft":
+        # the objective is the distance to the target AUDIO: no model, no embedding, nothing to compute once but the target's
+        # magnitude table, which the evaluator builds for the span it evaluates
+        evaluator = engine.MrstftEvaluator(input_audio, sample_rate, plugins, target_audio)
+        return _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel,
+                        dropout, savepop, run_dir, seed, rng, early_stop, None, "")
 
     # compute target embedding (only once)
     target_embed = embed_func(target_audio, model, sample_rate)
@@ -436,6 +444,31 @@ def run_es(
     # never forwards it to process_audio, so the population is rendered without per-stage normalisation here too)
     evaluator = engine.PopulationEvaluator(input_audio, sample_rate, plugins, model, eval_targets, embed_func=eval_embed_func,
                                            entry_weights=entry_weights)
+    return _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel,
+                    dropout, savepop, run_dir, seed, rng, early_stop, content_model, _CP)
+
+
+def _check_mrstft_run(input_audio, target_audio, plugins, content_model, dropout, savepop):
+    """What run_es(distance="mrstft") cannot do, said before anything is launched."""
+    if target_audio.dim() != 3 or target_audio.shape[0] != input_audio.shape[0] or target_audio.shape[-1] != input_audio.shape[-1]:
+        raise ValueError(f"distance 'mrstft' compares sample spans: the target {tuple(target_audio.shape)} must have the input's "
+                         f"batch and length {tuple(input_audio.shape)}")
+    c_out = engine.chain_out_channels(plugins, input_audio.shape[1])
+    if target_audio.shape[1] != c_out:
+        raise ValueError(f"distance 'mrstft': the target has {target_audio.shape[1]} channels, the chain renders {c_out}")
+    if content_model is not None:
+        raise ValueError("distance 'mrstft' has no embeddings: content_model cannot be used with it")
+    if dropout > 0:
+        raise ValueError("distance 'mrstft' has no embeddings: dropout must be 0")
+    if savepop:
+        raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
+
+
+def _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel, dropout,
+             savepop, run_dir, seed, rng, early_stop, content_model, _CP):
+    """run_es from its first evaluation on (reference 574-692), for whichever evaluator the distance chose: only losses are
+    seen here, so find_w0, the seeded draws, the early stop and the rank sharding are the same for every objective."""
+    _, rank, world = _dist_info()
     total_num_params = _chain_dims(evaluator, plugins)
 
     def evaluate(W, dropout: float = 0.0, want_audio: bool = False, while_waiting=None):
