@@ -1333,21 +1333,36 @@ static bool cnn14_fuse1r(const stito_cnn14_weights *w, int S, const int H[7], co
            w->channels[0] == 1 && stito_conv_block1_f2reg_supported(S, H[0], W[0], w->channels[1], w->channels[1], 1);
 }
 
+// The trunk's workspace on S streams of maps H x W, for stito_cnn14_workspace_bytes and stito_cnn14_forward alike, with the launch
+// decisions its size depends on (a new region is added here and nowhere else).
+struct TrunkLayout : WsLayout {
+    size_t actA, actB, feat, vbuf, vbytes, amax, amax_stride, chA, chB;
+    bool fuse1r;      // conv_block1 in one launch: cnn14_pre_bytes holds that launch's need whenever cnn14_fuse1r can say yes
+    ChunkPlan plan;   // planned from that fuse1r
+};
+static TrunkLayout cnn14_layout(const stito_cnn14_weights *w, int S, const int H[7], const int W[7]) {
+    size_t a = 0, b = 0;   // the largest output map of a block's first conv | of its second
+    for (int blk = 0; blk < 6; ++blk) {
+        a = std::max(a, (size_t)S * H[blk] * W[blk] * w->channels[blk + 1]);
+        b = std::max(b, (size_t)S * H[blk + 1] * W[blk + 1] * w->channels[blk + 1]);
+    }
+    TrunkLayout l;
+    l.fuse1r = cnn14_fuse1r(w, S, H, W);
+    l.plan = cnn14_chunk_plan(w, S, H, W, l.fuse1r);
+    l.actA = l.add(a * 4); l.actB = l.add(b * 4);
+    l.feat = l.add((size_t)S * w->channels[6] * 4);                 // the pooled features
+    l.vbuf = l.add(l.vbytes = cnn14_pre_bytes(w, S, H, W));         // the conv workspace
+    l.amax_stride = align_up((size_t)S * sizeof(unsigned), 256);    // per-stream output maxima, one buffer per conv (split-precision layers)
+    l.amax = l.add(l.amax_stride * STITO_CNN14_NUM_CONVS);
+    l.chA = l.add(l.plan.scratch_floats * 4); l.chB = l.add(l.plan.scratch_floats * 4);   // the chunked run's two scratch maps
+    l.total += 256;                                                 // pays for aligning the caller's base pointer up
+    return l;
+}
+
 extern "C" size_t stito_cnn14_workspace_bytes(const stito_cnn14_weights *w, int n_streams, int64_t n_frames) {
     int H[7], W[7];
     cnn14_dims(n_frames, w->n_mels, H, W);
-    size_t a = 0, b = 0;
-    for (int blk = 0; blk < 6; ++blk) {
-        const size_t full = (size_t)n_streams * H[blk] * W[blk] * w->channels[blk + 1];
-        const size_t pooled = (size_t)n_streams * H[blk + 1] * W[blk + 1] * w->channels[blk + 1];
-        a = full > a ? full : a;
-        b = pooled > b ? pooled : b;
-    }
-    const size_t feat = (size_t)n_streams * w->channels[6];
-    const ChunkPlan plan = cnn14_chunk_plan(w, n_streams, H, W, cnn14_fuse1r(w, n_streams, H, W));
-    return align_up(a * 4, 256) + align_up(b * 4, 256) + align_up(feat * 4, 256) + cnn14_pre_bytes(w, n_streams, H, W) +
-           STITO_CNN14_NUM_CONVS * align_up((size_t)n_streams * sizeof(unsigned), 256) + 256 +  // + per-stream output maxima, one buffer per conv (split-precision layers)
-           2 * align_up(plan.scratch_floats * 4, 256);                                         // + the chunked run's two scratch maps
+    return cnn14_layout(w, n_streams, H, W).total;
 }
 
 // ---- optional launch timing for bench.py: HIP events on the launch stream around the MFMA convs ----
@@ -1430,14 +1445,11 @@ struct Trunk {
     const stito_cnn14_weights *w;
     int H[7], W[7];
     void *stream;
-    void *vbuf;
-    size_t vbytes;
-    unsigned *amax_all;
-    size_t amax_stride;
+    TrunkLayout lay;   // of the workspace at ws (256-aligned)
+    char *ws;
     int n_cus;
-    bool fuse1r;
 
-    unsigned *amax_of(int conv, int s0) const { return (unsigned *)((char *)amax_all + amax_stride * conv) + s0; }
+    unsigned *amax_of(int conv, int s0) const { return (unsigned *)(ws + lay.amax + lay.amax_stride * conv) + s0; }
 
     // does conv i + 1 run a kernel that scales its transformed input by per-stream maxima of conv i's output?
     bool next_wants_amax(int i, int S) const {
@@ -1453,7 +1465,7 @@ struct Trunk {
         unsigned *amax_out = next_wants_amax(1, S) ? amax_of(1, s0) : nullptr;
         const int cout = w->channels[1];
         const int rc = stito_conv_block1_f2reg(in, w->conv1_f2reg_w_dev, w->conv_wino_dev[1], w->bn_scale_dev[1], w->bn_shift_dev[1], out,
-                                               S, H[0], W[0], cout, cout, 1, vbuf, vbytes, stream, amax_out);
+                                               S, H[0], W[0], cout, cout, 1, ws + lay.vbuf, lay.vbytes, stream, amax_out);
         if (rc) return rc;
         have_amax = amax_out != nullptr;
         return t.end();
@@ -1482,7 +1494,7 @@ struct Trunk {
         unsigned *amax_out = nullptr;
         if ((conv_algo(algo_i).reports_amax || (l.c.Cin == 1 && !l.pool)) && next_wants_amax(i, S)) amax_out = amax_of(i, s0);
         const int rc = conv3x3_ws(algo_i, ConvArgs{in, wino ? wino_w : w->conv_w_dev[i], w->bn_scale_dev[i], w->bn_shift_dev[i], out, l.c,
-                                                   l.pool != 0, vbuf, vbytes, (hipStream_t)stream,
+                                                   l.pool != 0, ws + lay.vbuf, lay.vbytes, (hipStream_t)stream,
                                                    (have_amax && i > 0) ? amax_of(i - 1, s0) : nullptr, amax_out, g_wino_trace});
         if (rc) return rc;
         have_amax = amax_out != nullptr;
@@ -1506,32 +1518,18 @@ extern "C" int stito_cnn14_forward(const stito_cnn14_weights *w, const float *lo
     STITO_REQUIRE(H[5] >= 1 && W[5] >= 1, STITO_E_INVALID,
                   "Given input size: (%dx%dx%d). Calculated output size is too small (audio shorter than 5 poolings)",
                   w->channels[5], H[4], W[4]);
-    STITO_REQUIRE(workspace_bytes >= stito_cnn14_workspace_bytes(w, S, n_frames), STITO_E_WORKSPACE, "cnn14 workspace too small");
-    size_t a = 0, b = 0;
-    for (int blk = 0; blk < 6; ++blk) {
-        const size_t full = (size_t)S * H[blk] * W[blk] * w->channels[blk + 1];
-        const size_t pooled = (size_t)S * H[blk + 1] * W[blk + 1] * w->channels[blk + 1];
-        a = full > a ? full : a;
-        b = pooled > b ? pooled : b;
-    }
-    char *ws = (char *)(((uintptr_t)workspace_dev + 255) & ~(uintptr_t)255);
-    float *actA = (float *)ws;
-    float *actB = (float *)(ws + align_up(a * 4, 256));
-    float *feat = (float *)(ws + align_up(a * 4, 256) + align_up(b * 4, 256));
-    tr.vbytes = cnn14_pre_bytes(w, S, H, W);
-    tr.vbuf = ws + align_up(a * 4, 256) + align_up(b * 4, 256) + align_up((size_t)S * w->channels[6] * 4, 256);
+    const TrunkLayout &lay = tr.lay = cnn14_layout(w, S, H, W);
+    STITO_REQUIRE(workspace_bytes >= lay.total, STITO_E_WORKSPACE, "cnn14 workspace too small");
+    char *ws = tr.ws = (char *)(((uintptr_t)workspace_dev + 255) & ~(uintptr_t)255);
+    float *actA = (float *)(ws + lay.actA), *actB = (float *)(ws + lay.actB), *feat = (float *)(ws + lay.feat);
+    float *chA = (float *)(ws + lay.chA), *chB = (float *)(ws + lay.chB);
     // per-stream output maxima, handed from a layer to the split-precision layer behind it: one buffer per conv, all zeroed by
     // ONE launch at the top of the pass (one per layer was ten more dispatches per pass)
-    tr.amax_stride = align_up((size_t)S * sizeof(unsigned), 256);
-    tr.amax_all = (unsigned *)((char *)tr.vbuf + tr.vbytes);
-    STITO_TRY(zero_async(tr.amax_all, tr.amax_stride * STITO_CNN14_NUM_CONVS, st));
+    STITO_TRY(zero_async(ws + lay.amax, lay.amax_stride * STITO_CNN14_NUM_CONVS, st));
     DeviceInfo dinfo;
     STITO_TRY(device_info(dinfo));   // cached per device
     tr.n_cus = dinfo.cus;
-    tr.fuse1r = cnn14_fuse1r(w, S, H, W) && tr.vbytes >= stito_conv_block1_f2reg_workspace_bytes(S, H[0], W[0], w->channels[1], w->channels[1], 1);
-    const ChunkPlan plan = cnn14_chunk_plan(w, S, H, W, tr.fuse1r);
-    float *chA = (float *)((char *)tr.amax_all + tr.amax_stride * STITO_CNN14_NUM_CONVS);   // the chunked run's two scratch maps
-    float *chB = (float *)((char *)chA + align_up(plan.scratch_floats * 4, 256));
+    const ChunkPlan &plan = lay.plan;
 
     const float *cur = logmel_dev;   // input of conv i
     bool have_amax = false;          // its producer reported the per-stream maxima
@@ -1550,7 +1548,7 @@ extern "C" int stito_cnn14_forward(const stito_cnn14_weights *w, const float *lo
                 bool camax = have_amax;
                 int flip = 0;
                 for (int k = plan.first; k <= plan.last;) {
-                    const bool b1 = k == 0 && tr.fuse1r;   // conv_block1's two convs are one launch writing conv 1's output
+                    const bool b1 = k == 0 && lay.fuse1r;   // conv_block1's two convs are one launch writing conv 1's output
                     const int k_out = b1 ? 1 : k;
                     float *o = k_out == plan.last ? run_out + (size_t)s0 * out_ps : (flip ? chB : chA);
                     if (b1) STITO_TRY(tr.block1(cin_ptr, o, sc, s0, camax));
@@ -1566,7 +1564,7 @@ extern "C" int stito_cnn14_forward(const stito_cnn14_weights *w, const float *lo
             i = plan.last + 1;
             continue;
         }
-        if (i == 0 && tr.fuse1r) {
+        if (i == 0 && lay.fuse1r) {
             STITO_TRY(tr.block1(cur, actB, S, 0, have_amax));
             cur = actB;
             i = 2;

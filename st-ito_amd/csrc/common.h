@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -40,6 +41,13 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// A device workspace as a row of 256-byte-aligned regions: add() returns the next region's offset.  An entry point's ONE layout
+// function fills a struct of offsets with it; the *_workspace_bytes query returns its `total`, the launcher takes ws + offset.
+struct WsLayout {
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t off = total; total += align_up(bytes, 256); return off; }
+};
 
 // Zero `bytes` (a multiple of 4, 4-byte aligned) on `st` with a KERNEL, never hipMemsetAsync: a memset node captured into a hipGraph
 // in front of a kernel that accumulates into the buffer (atomicMax of peaks / stream maxima) was not ordered in front of that kernel

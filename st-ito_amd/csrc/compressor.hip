@@ -62,10 +62,14 @@ static CompGeom comp_geometry(int64_t L) {
     return g;
 }
 
-size_t compressor_workspace_bytes(int n_streams, int64_t n_samples) {
-    const CompGeom g = comp_geometry(n_samples);
-    return align_up((size_t)n_streams * g.fn_stride * sizeof(float), 256) + align_up((size_t)n_streams * g.z_stride * sizeof(float), 256);
+struct CompLayout : WsLayout { size_t fn, z_end; };   // block functions | boundary states
+static CompLayout comp_layout(int n_streams, const CompGeom &g) {
+    CompLayout l;
+    l.fn = l.add((size_t)n_streams * g.fn_stride * sizeof(float));
+    l.z_end = l.add((size_t)n_streams * g.z_stride * sizeof(float));
+    return l;
 }
+size_t compressor_workspace_bytes(int n_streams, int64_t n_samples) { return comp_layout(n_streams, comp_geometry(n_samples)).total; }
 
 struct CompCoef {
     float thr, thr_inv, p, cat, crl, sg;
@@ -206,8 +210,8 @@ int compressor_stage(const InView &in, float *audio_dev, int64_t cand_stride, in
                      const double *coef, void *workspace, hipStream_t st) {
     const CompGeom g = comp_geometry(n_samples);
     const int S = pop * C;
-    float *fn = (float *)workspace;
-    float *z_end = (float *)((char *)workspace + align_up((size_t)S * g.fn_stride * sizeof(float), 256));
+    const CompLayout l = comp_layout(S, g);
+    float *fn = (float *)((char *)workspace + l.fn), *z_end = (float *)((char *)workspace + l.z_end);
     if (g.n_fn > 0) {
         hipLaunchKernelGGL(k_comp_blockfn, dim3((unsigned)((g.n_fn + CB_TILE - 1) / CB_TILE), S), dim3(256), 0, st, in, fn, g, C, coef);
         STITO_LAUNCH_CHECK();

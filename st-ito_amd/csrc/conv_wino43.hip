@@ -1712,7 +1712,7 @@ enum W43Kind { W43_PRE, W43_SPLIT, W43_SPLIT2, W43_SPLIT3 };
 // One launch of one of them, worked out once from (shape, pool): `supported`, `workspace_bytes`, `issued_flops`,
 // wino43_split3_workgroups and the launcher all read this, and the launcher's pointers are ws + region.off -- a region's size is
 // spelled in w43_plan and nowhere else.
-struct W43Plan {
+struct W43Plan : WsLayout {   // total: workspace bytes; 0: not covered, or no grid a launch can take
     struct Region { size_t off, bytes; };
     bool ok = false;         // the algorithm covers the shape
     Wino43Geom g;            // of the shape, as the transform pass takes it; the conv kernel's adds the four below (w43_conv_geom)
@@ -1722,8 +1722,7 @@ struct W43Plan {
     int xcd_m = 0;           // two and six sweeps: the XCDs as xcd_m item classes x 8 / xcd_m channel-tile ranges
     int64_t grid = 0;        // workgroups, whole XCD rounds (a launch with the sweeps split: one such grid per sweep); 0: none
     Region v{}, amax{}, partial{}, flags{};   // V slabs | stream maxima | partial outputs per item | hand-off flags or counts per item
-    size_t total = 0;        // workspace bytes; 0: not covered, or no grid a launch can take
-    void add(Region &r, size_t bytes) { r = Region{total, bytes}; total += align_up(bytes, 256); }
+    void add(Region &r, size_t bytes) { r = Region{WsLayout::add(bytes), bytes}; }
 };
 
 // whole XCD rounds: 8 XCDs x (groups of 32 / ct_group of an XCD's items) x (groups of ct_group channel tiles) x 32 workgroups

@@ -208,27 +208,30 @@ __global__ __launch_bounds__(CR_THREADS) void k_cr_mac_ifft(InView in, float *__
 
 static inline int cr_blocks(int64_t n) { return (int)((n + CR_B - 1) / CR_B); }
 
-size_t conv_reverb_workspace_bytes(int n_streams, int64_t n_samples, int64_t n_taps) {
-    const size_t spec = (size_t)CR_B * sizeof(float2);
-    return align_up(spec, 256) + align_up((size_t)n_streams * cr_blocks(n_samples) * spec, 256) +
-           align_up((size_t)n_streams * cr_blocks(n_taps) * spec, 256);
+static constexpr size_t CR_SPEC = (size_t)CR_B * sizeof(float2);   // bytes of one spectrum
+struct ConvReverbLayout : WsLayout { size_t tw, X, H; };   // twiddles | spectra of the input blocks | of the IR partitions
+static ConvReverbLayout conv_reverb_layout(int n_streams, int64_t n_samples, int64_t n_taps) {
+    ConvReverbLayout l;
+    l.tw = l.add(CR_SPEC);
+    l.X = l.add((size_t)n_streams * cr_blocks(n_samples) * CR_SPEC);
+    l.H = l.add((size_t)n_streams * cr_blocks(n_taps) * CR_SPEC);
+    return l;
 }
+size_t conv_reverb_workspace_bytes(int n_streams, int64_t n_samples, int64_t n_taps) { return conv_reverb_layout(n_streams, n_samples, n_taps).total; }
 
 int conv_reverb_stage(const InView &in, float *audio_dev, int64_t cand_stride, int pop, int64_t n_samples,
                       const double *coef, const float *noise_bank, int64_t n_taps, void *workspace, hipStream_t st) {
     STITO_REQUIRE(noise_bank != nullptr && n_taps >= 2, STITO_E_INVALID,
                   "NoiseShapedReverb needs its noise bank (aux_dev, (2, 12, n_taps) float32) and n_taps >= 2");
     const int S = pop * 2, J = cr_blocks(n_samples), K = cr_blocks(n_taps);
-    const size_t spec = (size_t)CR_B * sizeof(float2);
+    const ConvReverbLayout l = conv_reverb_layout(S, n_samples, n_taps);
     char *ws = (char *)workspace;
-    float2 *tw = (float2 *)ws;
-    float2 *X = (float2 *)(ws + align_up(spec, 256));
-    float2 *H = (float2 *)(ws + align_up(spec, 256) + align_up((size_t)S * J * spec, 256));
+    float2 *tw = (float2 *)(ws + l.tw), *X = (float2 *)(ws + l.X), *H = (float2 *)(ws + l.H);
     // an input shared by groups of candidates (first effect of the chain) is transformed once per group
     const bool shared = in.cand_stride == 0;
     const int group = shared ? (in.group < pop ? in.group : pop) : 0;
     const int n_in_streams = shared ? (pop / group) * 2 : S;
-    const size_t lds = 2 * spec;
+    const size_t lds = 2 * CR_SPEC;
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_cr_ir_fft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_cr_in_fft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_cr_mac_ifft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

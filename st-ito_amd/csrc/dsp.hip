@@ -962,48 +962,43 @@ extern "C" int stito_chain_num_dims(const stito_fx_desc *chain, int n_fx) {
     return d;
 }
 
-// convolution reverb: spectra of the input blocks and of every candidate's IR partitions
-static size_t conv_reverb_bytes(const stito_fx_desc *chain, int n_fx, int64_t n_samples, int pop) {
-    size_t cr = 0;
-    for (int i = 0; i < n_fx; ++i)
-        if (chain[i].kind == STITO_FX_NOISE_REVERB) {
-            const size_t need = conv_reverb_workspace_bytes(pop * 2, n_samples, chain[i].aux_len > 0 ? chain[i].aux_len : 1);
-            cr = need > cr ? need : cr;
-        }
-    return cr;
-}
-
 // Freeverb as two workgroups per candidate (k_reverb<true> + k_reverb_mix) while that still leaves every workgroup its own CU:
 // a population of 32 runs 64 half-size workgroups instead of 32 (0.81 -> see profiles/round6_small_pop.txt).  STITO_REVERB_SPLIT=0 / 1 forces.
 static bool reverb_split(int pop) {
     if (const char *e = getenv("STITO_REVERB_SPLIT")) return atoi(e) != 0;   // (read per call: the tests flip it)
     DeviceInfo d;
-    if (device_info(d) != STITO_OK) return false;
-    return 2 * pop <= d.cus;
-}
-static size_t reverb_split_bytes(const stito_fx_desc *chain, int n_fx, int64_t n_samples, int pop) {   // the wet signals (pop, 2, L)
-    bool has = false;
-    for (int i = 0; i < n_fx; ++i) has |= chain[i].kind == STITO_FX_REVERB;
-    return has && reverb_split(pop) ? align_up((size_t)pop * 2 * n_samples * sizeof(float), 256) : 0;
+    return device_info(d) == STITO_OK && 2 * pop <= d.cus;
 }
 
-// dasp compressor: its look-ahead reads x[n - 512] while y[n] is written, so it cannot work in place; a stage that reads audio_dev
-// renders into this (pop, 2, L) scratch copy instead
-static size_t dasp_comp_bytes(const stito_fx_desc *chain, int n_fx, int64_t n_samples, int pop) {
-    bool has = false;
-    for (int i = 0; i < n_fx; ++i) has |= chain[i].kind == STITO_FX_DASP_COMPRESSOR;
-    return has ? align_up((size_t)pop * 2 * n_samples * sizeof(float), 256) : 0;
+// The render workspace, for stito_render_workspace_bytes and the launcher alike (a new region is added here and nowhere else).
+struct RenderLayout : WsLayout {
+    size_t coef, comp, conv_reverb, reverb_wet, dasp_copy, stage_peaks;
+    bool rv_split;   // Freeverb as two workgroups per candidate: taken here, once per call, because reverb_wet is sized by it
+};
+static RenderLayout render_layout(const stito_fx_desc *chain, int n_fx, int64_t n_samples, int pop) {
+    bool has_comp = false, has_reverb = false, has_dasp = false;
+    size_t cr = 0;
+    for (int i = 0; i < n_fx; ++i) {
+        has_comp |= chain[i].kind == STITO_FX_COMPRESSOR;
+        has_reverb |= chain[i].kind == STITO_FX_REVERB;
+        has_dasp |= chain[i].kind == STITO_FX_DASP_COMPRESSOR;
+        if (chain[i].kind == STITO_FX_NOISE_REVERB) cr = std::max(cr, conv_reverb_workspace_bytes(pop * 2, n_samples, chain[i].aux_len > 0 ? chain[i].aux_len : 1));
+    }
+    const size_t stereo = (size_t)pop * 2 * n_samples * sizeof(float);   // a (pop, 2, L) signal
+    RenderLayout l;
+    l.rv_split = has_reverb && reverb_split(pop);
+    l.coef = l.add((size_t)(n_fx > 0 ? n_fx : 1) * pop * COEF_STRIDE * sizeof(double));
+    l.comp = l.add(has_comp ? compressor_workspace_bytes(pop * 2, n_samples) : 0);   // two channels per candidate whatever the chain does
+    l.conv_reverb = l.add(cr);                          // spectra of the input blocks and of every candidate's IR partitions
+    l.reverb_wet = l.add(l.rv_split ? stereo : 0);      // wet signals of the per-channel Freeverb
+    // the dasp compressor's look-ahead reads x[n - 512] while y[n] is written: a stage that reads audio_dev renders into this copy
+    l.dasp_copy = l.add(has_dasp ? stereo : 0);
+    l.stage_peaks = l.add((size_t)pop * sizeof(float));   // per-stage peaks (normalize_stages)
+    l.total += 256;                                       // pays for aligning the caller's base pointer up
+    return l;
 }
-
-extern "C" size_t stito_render_workspace_bytes(const stito_fx_desc *chain, int n_fx, int in_channels,
-                                               int64_t n_samples, int pop) {
-    (void)in_channels;  // the compressor's share is sized for two channels per candidate whatever the chain does
-    size_t coef = align_up((size_t)(n_fx > 0 ? n_fx : 1) * pop * COEF_STRIDE * sizeof(double), 256);
-    bool has_comp = false;
-    for (int i = 0; i < n_fx; ++i) has_comp |= chain[i].kind == STITO_FX_COMPRESSOR;
-    size_t env = has_comp ? compressor_workspace_bytes(pop * 2, n_samples) : 0;  // block functions + boundary states
-    return coef + env + conv_reverb_bytes(chain, n_fx, n_samples, pop) + reverb_split_bytes(chain, n_fx, n_samples, pop) +
-           dasp_comp_bytes(chain, n_fx, n_samples, pop) + align_up((size_t)pop * sizeof(float), 256) + 256;
+extern "C" size_t stito_render_workspace_bytes(const stito_fx_desc *chain, int n_fx, int /*in_channels*/, int64_t n_samples, int pop) {
+    return render_layout(chain, n_fx, n_samples, pop).total;
 }
 
 static int peak_strided(const float *audio_dev, int pop, int64_t per, int64_t stride, float *peaks_dev, hipStream_t st) {
@@ -1060,23 +1055,15 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
     const int dims = stito_chain_num_dims(chain, n_fx);
     STITO_REQUIRE(dims >= 0, STITO_E_INVALID, "Plugin must contain a known effect kind");
     STITO_REQUIRE(dims == n_dims, STITO_E_INVALID, "parameter vector has %d dims, chain consumes %d", n_dims, dims);
-    const size_t need = stito_render_workspace_bytes(chain, n_fx, in_channels, n_samples, pop);
-    STITO_REQUIRE(workspace_bytes >= need, STITO_E_WORKSPACE, "render workspace: have %zu need %zu", workspace_bytes, need);
+    const RenderLayout lay = render_layout(chain, n_fx, n_samples, pop);
+    STITO_REQUIRE(workspace_bytes >= lay.total, STITO_E_WORKSPACE, "render workspace: have %zu need %zu", workspace_bytes, lay.total);
     const int C_out = stito_chain_out_channels(chain, n_fx, in_channels);
     const int64_t L = n_samples;
     const int64_t cand_stride = (int64_t)C_out * L;
 
     char *ws = (char *)(((uintptr_t)workspace_dev + 255) & ~(uintptr_t)255);
-    double *coef = (double *)ws;
-    float *envbuf = (float *)(ws + align_up((size_t)(n_fx > 0 ? n_fx : 1) * pop * COEF_STRIDE * sizeof(double), 256));
-    bool has_comp = false;
-    for (int i = 0; i < n_fx; ++i) has_comp |= chain[i].kind == STITO_FX_COMPRESSOR;
-    char *crbuf = (char *)envbuf + (has_comp ? compressor_workspace_bytes(pop * 2, n_samples) : 0);
-    float *rvbuf = (float *)(crbuf + conv_reverb_bytes(chain, n_fx, n_samples, pop));   // wet signals of the per-channel Freeverb
-    const bool rv_split = reverb_split_bytes(chain, n_fx, n_samples, pop) > 0;
-    float *dcbuf = (float *)((char *)rvbuf + reverb_split_bytes(chain, n_fx, n_samples, pop));   // out-of-place copy of the dasp compressor
-    // per-stage peaks (normalize_stages) live in the last pop floats of the workspace
-    float *stage_peaks = (float *)(ws + (need - 256 - align_up((size_t)pop * sizeof(float), 256)));
+    double *coef = (double *)(ws + lay.coef);
+    float *rvbuf = (float *)(ws + lay.reverb_wet), *dcbuf = (float *)(ws + lay.dasp_copy), *stage_peaks = (float *)(ws + lay.stage_peaks);
 
     if (n_fx > 0) {
         ChainArgs args;
@@ -1128,7 +1115,7 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
                 break;
             }
             case STITO_FX_COMPRESSOR: {
-                const int rc = compressor_stage(in, audio_dev, cand_stride, pop, Cn, L, cf, envbuf, st);
+                const int rc = compressor_stage(in, audio_dev, cand_stride, pop, Cn, L, cf, ws + lay.comp, st);
                 if (rc) return rc;
                 break;
             }
@@ -1175,7 +1162,7 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
                 for (int k = 0; k < 16; ++k) minc = g.comb_size[k] < minc ? g.comb_size[k] : minc;
                 STITO_REQUIRE(mins >= RV_TT && minc >= 2 * RV_TT + RV_RUN && lds <= 160 * 1024, STITO_E_UNSUPPORTED,
                               "Reverb: sample rate %.0f needs delay lines outside the LDS-resident design", sample_rate);
-                if (rv_split) {
+                if (lay.rv_split) {
                     constexpr int NT = (RV_COMB_WAVES / 2 + RV_AP_WAVES / 2 + RV_STAGE_WAVES) * 64;
                     STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_reverb<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                     hipLaunchKernelGGL(k_reverb<true>, dim3(2 * pop), dim3(NT), lds, st, in, rvbuf, (int64_t)2 * L, L, cf, g);
@@ -1194,7 +1181,7 @@ extern "C" int stito_render_population_multi(const stito_fx_desc *chain, int n_f
             }
             case STITO_FX_NOISE_REVERB: {
                 STITO_REQUIRE(Cn == 2, STITO_E_INVALID, "NoiseShapedReverb must be declared with num_channels=2");
-                const int rc = conv_reverb_stage(in, audio_dev, cand_stride, pop, L, cf, fx.aux_dev, fx.aux_len, crbuf, st);
+                const int rc = conv_reverb_stage(in, audio_dev, cand_stride, pop, L, cf, fx.aux_dev, fx.aux_len, ws + lay.conv_reverb, st);
                 if (rc) return rc;
                 break;
             }

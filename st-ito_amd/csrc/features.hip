@@ -394,9 +394,18 @@ __global__ void k_lufs_gate_raw(const double *__restrict__ z, int n_items, int C
     lufs[item] = lufs_gate(z0, C == 2 ? z0 + n_blocks : nullptr, n_blocks);
 }
 
+// the meter's workspace: K-weighted audio (n, C, L) float32 | block energies (n, C, n_blocks) float64; C = 2 in stito_lufs (mono is duplicated)
+struct MeterLayout : WsLayout { size_t audio, z; };
+static MeterLayout meter_layout(int n_items, int channels, int64_t n_samples, int n_blocks) {
+    MeterLayout l;
+    l.audio = l.add((size_t)n_items * channels * n_samples * sizeof(float));
+    l.z = l.add((size_t)n_items * channels * n_blocks * sizeof(double));
+    return l;
+}
+
 extern "C" size_t stito_lufs_workspace_bytes(int n_items, int64_t n_samples, int n_blocks) {
     if (n_items <= 0 || n_samples <= 0 || n_blocks <= 0) return 0;
-    return align_up((size_t)n_items * 2 * n_samples * sizeof(float), 256) + align_up((size_t)n_items * 2 * n_blocks * sizeof(double), 256);
+    return meter_layout(n_items, 2, n_samples, n_blocks).total;
 }
 
 extern "C" int stito_lufs(const float *audio_dev, int n_items, int channels, int64_t n_samples, const double *kweight_coef_dev,
@@ -406,10 +415,10 @@ extern "C" int stito_lufs(const float *audio_dev, int n_items, int channels, int
     STITO_REQUIRE(n_items > 0 && n_samples > 0 && n_blocks > 0, STITO_E_INVALID, "stito_lufs: empty input");
     STITO_REQUIRE(channels == 1 || channels == 2, STITO_E_INVALID, "Invalid number of channels: %d", channels);
     STITO_REQUIRE(n_samples < (1ll << 31), STITO_E_UNSUPPORTED, "stito_lufs: %lld samples", (long long)n_samples);
-    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= stito_lufs_workspace_bytes(n_items, n_samples, n_blocks), STITO_E_WORKSPACE,
-                  "stito_lufs: workspace too small");
-    float *xn = (float *)workspace_dev;
-    double *z = (double *)((char *)workspace_dev + align_up((size_t)n_items * 2 * n_samples * sizeof(float), 256));
+    const MeterLayout l = meter_layout(n_items, 2, n_samples, n_blocks);
+    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= l.total, STITO_E_WORKSPACE, "stito_lufs: workspace too small");
+    float *xn = (float *)((char *)workspace_dev + l.audio);
+    double *z = (double *)((char *)workspace_dev + l.z);
     const int gx = (int)((n_samples + 256 * 16 - 1) / (256 * 16));
     hipLaunchKernelGGL(k_lufs_prep, dim3(gx < 1 ? 1 : (gx > 1024 ? 1024 : gx), n_items), dim3(256), 0, st, audio_dev, channels, n_samples, xn);
     STITO_LAUNCH_CHECK();
@@ -426,8 +435,7 @@ extern "C" int stito_lufs(const float *audio_dev, int n_items, int channels, int
 
 extern "C" size_t stito_lufs_raw_workspace_bytes(int n_items, int channels, int64_t n_samples, int n_blocks) {
     if (n_items <= 0 || channels <= 0 || n_samples <= 0 || n_blocks <= 0) return 0;
-    return align_up((size_t)n_items * channels * n_samples * sizeof(float), 256) +
-           align_up((size_t)n_items * channels * n_blocks * sizeof(double), 256);
+    return meter_layout(n_items, channels, n_samples, n_blocks).total;
 }
 
 extern "C" int stito_lufs_raw(const float *audio_dev, int n_items, int channels, int64_t n_samples, const double *kweight_coef_dev,
@@ -437,10 +445,10 @@ extern "C" int stito_lufs_raw(const float *audio_dev, int n_items, int channels,
     STITO_REQUIRE(n_items > 0 && n_samples > 0 && n_blocks > 0, STITO_E_INVALID, "stito_lufs_raw: empty input");
     STITO_REQUIRE(channels == 1 || channels == 2, STITO_E_INVALID, "Invalid number of channels: %d", channels);
     STITO_REQUIRE(n_samples < (1ll << 31), STITO_E_UNSUPPORTED, "stito_lufs_raw: %lld samples", (long long)n_samples);
-    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= stito_lufs_raw_workspace_bytes(n_items, channels, n_samples, n_blocks),
-                  STITO_E_WORKSPACE, "stito_lufs_raw: workspace too small");
-    float *y = (float *)workspace_dev;
-    double *z = (double *)((char *)workspace_dev + align_up((size_t)n_items * channels * n_samples * sizeof(float), 256));
+    const MeterLayout l = meter_layout(n_items, channels, n_samples, n_blocks);
+    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= l.total, STITO_E_WORKSPACE, "stito_lufs_raw: workspace too small");
+    float *y = (float *)((char *)workspace_dev + l.audio);
+    double *z = (double *)((char *)workspace_dev + l.z);
     InView in{audio_dev, (int64_t)channels * n_samples, n_samples, channels};
     STITO_TRY(eq_cascade(in, y, n_items, channels, n_samples, kweight_coef_dev, st));
     hipLaunchKernelGGL(k_lufs_blocks, dim3(n_blocks, n_items * channels), dim3(256), 0, st, (const float *)y, n_samples, block_lo_dev,

@@ -16,8 +16,6 @@
 #include "dsp_view.h"
 #include "juce_comp.h"
 
-extern "C" size_t stito_lufs_raw_workspace_bytes(int n_items, int channels, int64_t n_samples, int n_blocks);
-
 namespace stito {
 
 // ---- Savitzky-Golay, mode "interp" ---------------------------------------------------------------------------------------
@@ -276,19 +274,15 @@ __global__ void k_climb_update(const double *__restrict__ lufs, const double *__
     active[i] = (d > CLIMB_TOL_LU && t > CLIMB_FLOOR_DB) ? 1 : 0;
 }
 
-struct ClimbLayout {
-    size_t coef, comp, scratch, peaks, lufs, meter, total;
-};
-
+struct ClimbLayout : WsLayout { size_t coef, comp, scratch, peaks, lufs, meter; };
 static ClimbLayout climb_layout(int n_items, int C, int64_t n, int n_blocks) {
     ClimbLayout l;
-    l.coef = 0;
-    l.comp = l.coef + align_up((size_t)n_items * COEF_STRIDE * sizeof(double), 256);
-    l.scratch = l.comp + align_up(compressor_workspace_bytes(n_items * C, n), 256);
-    l.peaks = l.scratch + align_up((size_t)n_items * C * n * sizeof(float), 256);
-    l.lufs = l.peaks + align_up((size_t)n_items * sizeof(float), 256);
-    l.meter = l.lufs + align_up((size_t)n_items * sizeof(double), 256);
-    l.total = l.meter + align_up(stito_lufs_raw_workspace_bytes(n_items, C, n, n_blocks), 256);
+    l.coef = l.add((size_t)n_items * COEF_STRIDE * sizeof(double));
+    l.comp = l.add(compressor_workspace_bytes(n_items * C, n));
+    l.scratch = l.add((size_t)n_items * C * n * sizeof(float));
+    l.peaks = l.add((size_t)n_items * sizeof(float));
+    l.lufs = l.add((size_t)n_items * sizeof(double));
+    l.meter = l.add(stito_lufs_raw_workspace_bytes(n_items, C, n, n_blocks));
     return l;
 }
 
@@ -377,9 +371,8 @@ extern "C" int stito_climb_step(float *audio_dev, int n_items, int channels, int
     const ClimbLayout l = climb_layout(n_items, channels, n_samples, n_blocks);
     STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= l.total, STITO_E_WORKSPACE, "stito_climb_step: workspace too small");
     char *ws = (char *)workspace_dev;
-    double *coef = (double *)(ws + l.coef);
+    double *coef = (double *)(ws + l.coef), *lufs = (double *)(ws + l.lufs);
     float *scratch = (float *)(ws + l.scratch), *peaks = (float *)(ws + l.peaks);
-    double *lufs = (double *)(ws + l.lufs);
     const int64_t per = (int64_t)channels * n_samples;
     hipLaunchKernelGGL(k_climb_coef, dim3((n_items + 63) / 64), dim3(64), 0, st, (const double *)threshold_dev, n_items, sample_rate, coef);
     STITO_LAUNCH_CHECK();
