@@ -110,7 +110,7 @@ int stito_version(void);
  * 10.0 runs unchanged): 1 = stito_gather_crops; 2 = STITO_FX_DASP_EQ, _DASP_COMPRESSOR, _DASP_DISTORTION (kinds 8 - 10 of
  * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits); 3 = stito_barkspectrum_mixed,
  * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan; 4 = stito_mrstft_table_floats, stito_mrstft_target,
- * stito_mrstft_workspace_bytes, stito_mrstft_loss. */
+ * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -531,13 +531,26 @@ int stito_gather_crops(const float *packed_dev, int64_t packed_floats, const int
  * candidate's magnitudes never leave the CU; per-tile sums (float64) go to the workspace (stito_mrstft_workspace_bytes, 8-byte
  * aligned) and a second launch adds them in a fixed order: no atomics, and a candidate's loss has the same bits at every position
  * of every batch, for every n_targets.  The table kernel and the candidate kernel share the FFT and magnitude code, so
- * loss(y, table(y)) with norm_passes 0 is exactly 0.  The size functions return 0 for arguments the launches refuse. */
+ * loss(y, table(y)) with norm_passes 0 is exactly 0.  The size functions return 0 for arguments the launches refuse.
+ *
+ * stito_mrstft_loss_slots (ABI 10.5): stito_mrstft_loss for a SUBSET of the table's targets.  The population is n_slots stacked
+ * populations of pop / n_slots candidates (pop % n_slots == 0); candidate p belongs to population k = p / (pop / n_slots) and is
+ * scored against table target target_slot_dev[k] (n_slots int32 on the device): any subset of the n_targets targets, in any order,
+ * repeats allowed -- the batch whose stopped pairs drop out without the table being rebuilt.  A slot outside [0, n_targets) gives
+ * NaN for that population's losses, reads nothing from the table and leaves the other populations' bits as they are (the contract
+ * of stito_gather_crops for a slot that names no pair).  Workspace: stito_mrstft_workspace_bytes(pop, ...), as before.  Same
+ * kernels, same fixed-order sums: a candidate's loss has the same bits under every slot list as under stito_mrstft_loss on a table
+ * that holds only its target, and stito_mrstft_loss is this call with the identity map (n_slots = n_targets, slot k = k). */
 int64_t stito_mrstft_table_floats(const int *res, int n_res, int rows, int64_t n_samples);
 int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev, void *stream);
 size_t stito_mrstft_workspace_bytes(const int *res, int n_res, int pop, int channels, int64_t n_samples);
 int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                       const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
                       void *workspace_dev, size_t workspace_bytes, void *stream);
+int stito_mrstft_loss_slots(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                            const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
+                            int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
+                            void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

@@ -179,12 +179,22 @@ __device__ __forceinline__ float mr_magnitude(const MrDev &d, const float2 *buf,
     return sqrtf(fmaxf(fmaf(re, re, im * im), 1e-8f));
 }
 
+// Table target of candidate `cand`: population k = cand / per_target reads target slots[k], or target k when there is no slot
+// list (the identity map: stito_mrstft_loss).  -1 for a slot that names no target of the table.
+__device__ __forceinline__ int mr_target_of(int64_t cand, int per_target, const int32_t *__restrict__ slots, int n_targets) {
+    const int k = (int)(cand / per_target);
+    const int t = slots != nullptr ? slots[k] : k;
+    return (t >= 0 && t < n_targets) ? t : -1;
+}
+
 // TARGET: audio = y (rows, n); writes the magnitudes and the tile's sum |Y|^2 (K = 1 partial).
-// else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row (cand / per_target) * C + ch;
-//         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).
+// else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row mr_target_of(cand) * C + ch;
+//         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).  A candidate whose slot names no target
+//         reads nothing from the table and writes no partial: k_mrstft_final gives it NaN.
 template <bool TARGET>
 __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__restrict__ audio, const float *__restrict__ peaks,
-                                                      int norm_passes, int C, int per_target) {
+                                                      int norm_passes, int C, int per_target, const int32_t *__restrict__ slots,
+                                                      int n_targets) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int N = d.N, N2 = d.N2;
     double *red = (double *)smem_raw;                          // [2][MR_THREADS]
@@ -203,8 +213,10 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__r
     int64_t trow = row;
     if (!TARGET) {
         const int64_t cand = row / C;
+        const int t = mr_target_of(cand, per_target, slots, n_targets);
+        if (t < 0) return;  // the whole workgroup (one row, one candidate), before it loads anything
         if (peaks != nullptr && norm_passes > 0) r1 = 1.0f / fmaxf(peaks[cand], 1e-8f);  // x * (1 / d), as stito_logmel
-        trow = (cand / per_target) * C + (row - cand * C);
+        trow = (int64_t)t * C + (row - cand * C);
     }
     const float *x = audio + row * d.n;
 
@@ -296,12 +308,18 @@ __global__ void k_mrstft_target_sum(MrSum s, const double *__restrict__ partial,
 
 // one wave per candidate: lane (resolution, channel) adds its tiles in order, lane 0 the means in order
 __global__ __launch_bounds__(64) void k_mrstft_final(MrSum s, const double *__restrict__ partial, const double *__restrict__ ysum, int C,
-                                                     int per_target, float *__restrict__ loss) {
+                                                     int per_target, const int32_t *__restrict__ slots, int n_targets,
+                                                     float *__restrict__ loss) {
     __shared__ double term[64];
     const int cand = blockIdx.x, lane = threadIdx.x;
+    const int tgt = mr_target_of(cand, per_target, slots, n_targets);
+    if (tgt < 0) {  // the whole wave: no partial was written for this candidate and none is read
+        if (lane == 0) loss[cand] = __builtin_nanf("");
+        return;
+    }
     if (lane < s.n_res * C) {
         const int r = lane / C, ch = lane - r * C;
-        const int64_t row = (int64_t)cand * C + ch, trow = (int64_t)(cand / per_target) * C + ch;
+        const int64_t row = (int64_t)cand * C + ch, trow = (int64_t)tgt * C + ch;
         const double *p = partial + (row * s.tiles_total + s.tile_off[r]) * 2;
         double d2 = 0.0, lg = 0.0;
         for (int t = 0; t < s.tiles[r]; ++t) { d2 += p[2 * t]; lg += p[2 * t + 1]; }
@@ -378,7 +396,7 @@ extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev
         STITO_LAUNCH_CHECK();
         STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
         hipLaunchKernelGGL(k_mrstft<true>, dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
-                           (const float *)nullptr, 0, 1, 1);
+                           (const float *)nullptr, 0, 1, 1, (const int32_t *)nullptr, rows);
         STITO_LAUNCH_CHECK();
     }
     const int64_t n_sums = (int64_t)rows * p.n_res;
@@ -387,36 +405,57 @@ extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev
     return STITO_OK;
 }
 
-extern "C" int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
-                                 const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
-                                 void *workspace_dev, size_t workspace_bytes, void *stream) {
+// The one launch path of the loss: populations of pop / n_slots candidates, population k against target target_slot[k] of the
+// table's n_targets, or against target k when there is no slot list (then n_slots == n_targets).
+static int mr_loss(const char *who, const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                   const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
+                   int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
     STITO_TRY(mr_plan(res, n_res, n_samples, p));
     STITO_TRY(mr_device_fits(p));
-    STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "stito_mrstft_loss: pop %d, n_targets %d", pop, n_targets);
-    STITO_REQUIRE(pop % n_targets == 0, STITO_E_INVALID, "stito_mrstft_loss: population %d is not a multiple of the number of targets %d", pop, n_targets);
+    STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "%s: pop %d, n_targets %d", who, pop, n_targets);
+    STITO_REQUIRE(n_slots >= 1, STITO_E_INVALID, "%s: %d target slots", who, n_slots);
+    STITO_REQUIRE(pop % n_slots == 0, STITO_E_INVALID, "%s: population %d is not a multiple of the number of targets %d", who, pop, n_slots);
     STITO_REQUIRE(channels >= 1 && channels <= MR_MAX_CH && n_res * channels <= 64, STITO_E_INVALID, "Invalid number of channels: %d", channels);
-    STITO_REQUIRE(norm_passes == 0 || norm_passes == 1, STITO_E_INVALID, "stito_mrstft_loss: norm_passes %d must be 0 or 1", norm_passes);
-    STITO_REQUIRE(norm_passes == 0 || peaks_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss: norm_passes 1 needs the peaks");
-    STITO_REQUIRE(audio_dev != nullptr && table_dev != nullptr && loss_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss: null pointer");
-    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "stito_mrstft_loss: the table must be 16-byte aligned");
+    STITO_REQUIRE(norm_passes == 0 || norm_passes == 1, STITO_E_INVALID, "%s: norm_passes %d must be 0 or 1", who, norm_passes);
+    STITO_REQUIRE(norm_passes == 0 || peaks_dev != nullptr, STITO_E_INVALID, "%s: norm_passes 1 needs the peaks", who);
+    STITO_REQUIRE(audio_dev != nullptr && table_dev != nullptr && loss_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);
+    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "%s: the table must be 16-byte aligned", who);
     const int64_t rows = (int64_t)pop * channels, trows = (int64_t)n_targets * channels;
     const size_t need = (size_t)rows * p.tiles_total * 2 * sizeof(double);
-    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= need, STITO_E_WORKSPACE, "stito_mrstft_loss: workspace of %zu bytes, %zu needed",
+    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= need, STITO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
                   workspace_bytes, need);
-    STITO_REQUIRE(((uintptr_t)workspace_dev & 7) == 0, STITO_E_INVALID, "stito_mrstft_loss: the workspace must be 8-byte aligned");
+    STITO_REQUIRE(((uintptr_t)workspace_dev & 7) == 0, STITO_E_INVALID, "%s: the workspace must be 8-byte aligned", who);
+    for (int i = 0; i < p.n_res; ++i)
+        STITO_REQUIRE(rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "%s: too many tiles", who);
     double *partial = (double *)workspace_dev;
     const double *ysum = (const double *)(table_dev + p.mags_base + trows * p.row_floats);
     for (int i = 0; i < p.n_res; ++i) {
-        STITO_REQUIRE(rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "stito_mrstft_loss: too many tiles");
         const MrDev d = mr_dev(p, i, n_samples, (float *)table_dev, partial, 2);
         STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
         hipLaunchKernelGGL(k_mrstft<false>, dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev, peaks_dev,
-                           norm_passes, channels, pop / n_targets);
+                           norm_passes, channels, pop / n_slots, target_slot_dev, n_targets);
         STITO_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_mrstft_final, dim3((unsigned)pop), dim3(64), 0, st, mr_sum(p), partial, ysum, channels, pop / n_targets, loss_dev);
+    hipLaunchKernelGGL(k_mrstft_final, dim3((unsigned)pop), dim3(64), 0, st, mr_sum(p), partial, ysum, channels, pop / n_slots,
+                       target_slot_dev, n_targets, loss_dev);
     STITO_LAUNCH_CHECK();
     return STITO_OK;
+}
+
+extern "C" int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                                 const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
+                                 void *workspace_dev, size_t workspace_bytes, void *stream) {
+    return mr_loss("stito_mrstft_loss", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets, pop,
+                   channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int stito_mrstft_loss_slots(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                                       const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
+                                       int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
+                                       void *stream) {
+    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots: null target_slot_dev");
+    return mr_loss("stito_mrstft_loss_slots", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots,
+                   pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }

@@ -110,8 +110,6 @@ def main(argv=None):
     os.makedirs(run_dir, exist_ok=True)
 
     if args.objective == "mrstft":
-        if args.staged:
-            raise NotImplementedError("--objective mrstft is built for run_es only, not --staged")
         model, embed_func = None, None  # the distance is taken on the audio: no checkpoint
     else:
         model = make_synthetic_param_model(seed=0) if args.synthetic else load_param_model(ckpt_path=args.ckpt, use_gpu=args.use_gpu)

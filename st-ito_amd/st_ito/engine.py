@@ -587,7 +587,9 @@ class MrstftEvaluator:
     (evaluate takes the B populations stacked pair-major, like PopulationEvaluator).  The length policy is the embedding
     objective's (style_transfer.py:505-518) and the target receives the same span: the same zero padding to 262144, the same
     crop, and under random_crop the same start -- its table is rebuilt for that crop, one launch sequence on its C' rows.
-    Launches are eager."""
+    evaluate(W, pairs=[...], x=buffer, y=buffer) scores the populations of a SUBSET of the pairs on ready-made buffers, the
+    counterpart of PopulationEvaluator.evaluate(W, pairs=, x=) -- the ragged batch; `rendered_candidates` counts what went
+    through the render.  Launches are eager."""
 
     def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor,
                  device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False):
@@ -613,8 +615,10 @@ class MrstftEvaluator:
         self.x_full = x.to(self.device, torch.float32).contiguous()
         self.y_full = target_audio.to(self.device, torch.float32).contiguous()
         self._padded = None    # (x, y) zero padded to 262144, built once
-        self._targets = {}     # evaluate-time length -> MrstftTarget (its table is refilled when the span moves)
+        self._targets = {}     # evaluate-time length -> MrstftTarget of a cropped span (its table is refilled when the crop moves)
         self._table_span = {}  # evaluate-time length -> the span the table currently holds
+        self._static = {}      # evaluate-time length -> (MrstftTarget of all targets whose spans never move, {pair: slot})
+        self._moving = {}      # (evaluate-time length, number of pairs) -> MrstftTarget that every subset call with y refills
         self.rendered_candidates = 0
 
     def _spans(self, random_crop: bool, rng, parallel: bool):
@@ -633,9 +637,51 @@ class MrstftEvaluator:
             self._padded = (pad(x), pad(y))
         return (*self._padded, ("pad",))
 
+    def set_static_targets(self, length: int, pairs, y: torch.Tensor) -> None:
+        """The static table of one evaluate-time length, for an evaluator whose own audio is a stand-in (the ragged batch): y
+        (len(pairs), C', length) float32 on the device holds the target spans of the listed pairs, which never move.  Built
+        once; evaluate(W, pairs=, x=) without y then scores any subset of these pairs through the slot list."""
+        from . import features as _features
+
+        pairs = [int(b) for b in pairs]
+        if len(set(pairs)) != len(pairs) or any(not 0 <= b < self.n_inputs for b in pairs):
+            raise ValueError(f"pairs {pairs} do not name targets 0 .. {self.n_inputs - 1}")
+        if y.dim() != 3 or y.shape[0] != len(pairs) or y.shape[-1] != int(length):
+            raise ValueError(f"y must be ({len(pairs)}, chs, {int(length)}), got {tuple(y.shape)}")
+        self._static[int(length)] = (_features.MrstftTarget(y, self.resolutions), {b: k for k, b in enumerate(pairs)})
+
+    def _static_table(self, length: int, y: Optional[torch.Tensor] = None):
+        """-> (MrstftTarget, {pair: slot}) of ALL the targets at an evaluate-time length where no span moves: what
+        set_static_targets registered, else the evaluator's own targets (y, if the caller has them at hand) as they are or zero
+        padded to 262144 (built once)."""
+        from . import features as _features
+
+        ent = self._static.get(length)
+        if ent is None:
+            n = self.y_full.shape[-1]
+            if y is not None:
+                pass
+            elif length == n:
+                y = self.y_full
+            elif n < length == CROP_LEN:
+                y = torch.nn.functional.pad(self.y_full, (0, length - n)).contiguous()
+            else:
+                raise ValueError(f"no static targets of {length} samples (the evaluator's own have {n}): pass y")
+            ent = self._static[length] = (_features.MrstftTarget(y, self.resolutions), {b: b for b in range(self.n_inputs)})
+        return ent
+
     def evaluate(self, W, random_crop: bool = False, rng=np.random, want_audio: bool = False, dropout: float = 0.0,
-                 parallel: bool = False):
-        """Fitness of every row of W -> (loss (P,), {}, normalised audio or None)."""
+                 parallel: bool = False, pairs=None, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
+        """Fitness of every row of W -> (loss (P,), {}, normalised audio or None).
+
+        pairs / x: as PopulationEvaluator.evaluate -- the stacked populations of the listed pairs, in that order, on a
+        ready-made input buffer (len(pairs), C, L) used as it is (nothing drawn from rng); without x the listed pairs are taken
+        from the evaluator's own audio by the length policy.  The target side of a subset call:
+        y given -- (len(pairs), C', L), the target spans of exactly the listed pairs, for spans that move from call to call:
+            the table is refilled for these len(pairs) targets and population k is scored against target k;
+        y not given -- spans that never move: the table of ALL targets of that length is built once (_static_table) and the
+            subset goes through stito_mrstft_loss_slots, the slot list being the few int32 uploaded per call.  (Without x, a
+            span that the length policy crops is treated as moving: its target crops are taken like the inputs.)"""
         from . import features as _features
 
         if dropout > 0.0:
@@ -644,22 +690,70 @@ class MrstftEvaluator:
         if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
             raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
         P = Wn.shape[0]
+        if pairs is not None or x is not None or y is not None:
+            return self._evaluate_subset(Wn, random_crop, rng, want_audio, parallel, pairs, x, y)
         if P == 0 or P % self.n_inputs:
             raise ValueError(f"{P} candidates cannot be split over {self.n_inputs} inputs")
         x, y, span = self._spans(random_crop, rng, parallel)
         length = x.shape[-1]
+        if span[0] != "crop":   # the span never moves: the one static table of this length, shared with the subset calls
+            return self._score(Wn, x, self._static_table(length, y)[0], None, want_audio)
         tgt = self._targets.get(length)
         if tgt is None:
             tgt = self._targets[length] = _features.MrstftTarget(y, self.resolutions)
         elif self._table_span[length] != span:
             tgt.update(y)
         self._table_span[length] = span
+        return self._score(Wn, x, tgt, None, want_audio)
+
+    def _score(self, Wn, x, tgt, slots, want_audio):
+        """render -> loss against the table `tgt` (through the slot list, if there is one)"""
         Wt = torch.from_numpy(Wn).to(self.device)
         xin = x[0] if x.shape[0] == 1 else x
         audio, peaks = render_population(self.plugins, xin, Wt, self.sample_rate, chain=self.chain)
-        self.rendered_candidates += P
-        loss = tgt.loss(audio, peaks, norm_passes=1)
+        self.rendered_candidates += Wn.shape[0]
+        loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots)
         return loss, {}, (normalize_audio_(audio, peaks) if want_audio else None)
+
+    def _evaluate_subset(self, Wn, random_crop, rng, want_audio, parallel, pairs, x, y):
+        from . import features as _features
+
+        pairs = list(range(self.n_inputs)) if pairs is None else [int(b) for b in pairs]
+        if not pairs or any(not 0 <= b < self.n_inputs for b in pairs):
+            raise ValueError(f"pairs {pairs} do not name inputs 0 .. {self.n_inputs - 1}")
+        k, P = len(pairs), Wn.shape[0]
+        if P == 0 or P % k:
+            raise ValueError(f"{P} candidates cannot be split over {k} inputs")
+
+        def ready_made(t, name):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous() and t.shape[0] == k):
+                raise ValueError(f"{name} must be a contiguous ({k}, chs, n) float32 tensor on the GPU")
+
+        if x is None:
+            if y is not None:
+                raise ValueError("y (ready-made target spans) needs x (the input spans they belong to)")
+            xa, ya, span = self._spans(random_crop, rng, parallel)
+            x = xa[pairs].contiguous()
+            if span[0] == "crop":
+                y = ya[pairs].contiguous()
+        else:
+            ready_made(x, "x")
+        length = x.shape[-1]
+        if y is None:   # static spans: the table of all targets, the subset through the slot list
+            tgt, slot_of = self._static_table(length)
+            if any(b not in slot_of for b in pairs):
+                raise ValueError(f"pairs {pairs}: the static table of {length} samples holds the targets of {sorted(slot_of)}")
+            slots = torch.tensor([slot_of[b] for b in pairs], dtype=torch.int32).to(self.device)
+            return self._score(Wn, x, tgt, slots, want_audio)
+        ready_made(y, "y")
+        if y.shape[-1] != length:
+            raise ValueError(f"y has {y.shape[-1]} samples, x {length}")
+        tgt = self._moving.get((length, k))   # moving spans: refilled for exactly these targets, identity map
+        if tgt is None:
+            tgt = self._moving[(length, k)] = _features.MrstftTarget(y, self.resolutions)
+        else:
+            tgt.update(y)
+        return self._score(Wn, x, tgt, None, want_audio)
 
     def nan_warning(self) -> Optional[str]:
         return None

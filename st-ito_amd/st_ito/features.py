@@ -305,9 +305,11 @@ class MrstftTarget:
                                                   _hip.ptr(self.table), _hip.stream_ptr()))
         return self
 
-    def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0) -> torch.Tensor:
+    def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None) -> torch.Tensor:
         """audio (P, C, n) float32 on the GPU, P a multiple of the number of targets (candidate p against target p // (P // T))
-        -> (P,) float32.  norm_passes 1: audio[p] / clip(peaks[p], 1e-8) is what gets scored, folded into the kernel's loader."""
+        -> (P,) float32.  norm_passes 1: audio[p] / clip(peaks[p], 1e-8) is what gets scored, folded into the kernel's loader.
+        slots: (K,) int32 on the GPU, P a multiple of K -- the K stacked populations are scored against the targets slots[k] of
+        the table (stito_mrstft_loss_slots: any subset, any order; a slot that names no target gives NaN)."""
         from .engine import _WS
 
         if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
@@ -318,9 +320,16 @@ class MrstftTarget:
         L = _hip.lib()
         ws = _WS.get("mrstft", L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device)
         out = torch.empty(P, dtype=torch.float32, device=audio.device)
-        _hip.check(L.stito_mrstft_loss(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
-                                       self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(),
-                                       _hip.stream_ptr()))
+        if slots is None:
+            _hip.check(L.stito_mrstft_loss(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+                                           self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(),
+                                           _hip.stream_ptr()))
+            return out
+        if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
+            raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
+        _hip.check(L.stito_mrstft_loss_slots(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+                                             self.n_targets, _hip.ptr(slots), slots.numel(), P, self.channels, self.n, _hip.ptr(out),
+                                             _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
         return out
 
 

@@ -464,6 +464,34 @@ def _check_mrstft_run(input_audio, target_audio, plugins, content_model, dropout
         raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
 
 
+def _check_mrstft_staged(input_audio, target_audio, plugins, savepop):
+    """What run_staged_es(distance="mrstft") cannot do, said before anything is launched: every stage compares its sub-chain's
+    render with the full target, so every sub-chain has to render the target's channel count."""
+    if target_audio.dim() != 3 or target_audio.shape[0] != input_audio.shape[0] or target_audio.shape[-1] != input_audio.shape[-1]:
+        raise ValueError(f"distance 'mrstft' compares sample spans: the target {tuple(target_audio.shape)} must have the input's "
+                         f"batch and length {tuple(input_audio.shape)}")
+    names = list(plugins.keys())
+    for stage_idx in range(len(names)):
+        c_out = engine.chain_out_channels({k: plugins[k] for k in names[: stage_idx + 1]}, input_audio.shape[1])
+        if c_out != target_audio.shape[1]:
+            raise ValueError(f"distance 'mrstft': stage {stage_idx} ({names[stage_idx]}) renders {c_out} channels, the target has "
+                             f"{target_audio.shape[1]}")
+    if savepop:
+        raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
+
+
+def _check_mrstft_batch(input_audios, target_audios, plugins):
+    """What run_es_batch(distance="mrstft") cannot do, said before anything is launched; both forms (the rows of a (B, chs, n)
+    tensor are its pairs)."""
+    for b, (x, t) in enumerate(zip(input_audios, target_audios)):
+        if t.shape[-1] != x.shape[-1]:
+            raise ValueError(f"distance 'mrstft' compares sample spans: target {b} has {t.shape[-1]} samples, its input {x.shape[-1]}: "
+                             f"the lengths of a pair must be equal")
+        c_out = engine.chain_out_channels(plugins, x.shape[0])
+        if t.shape[0] != c_out:
+            raise ValueError(f"distance 'mrstft': target {b} has {t.shape[0]} channels, the chain renders {c_out}")
+
+
 def _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel, dropout,
              savepop, run_dir, seed, rng, early_stop, content_model, _CP):
     """run_es from its first evaluation on (reference 574-692), for whichever evaluator the distance chose: only losses are
@@ -559,17 +587,23 @@ def run_staged_es(
     PopulationEvaluator like run_es does (same length policy, same loss: mean over the embed_func dict of
     -cosine), input and target peak-normalised in place like run_es (452-453), population sharded over the
     ranks like run_es.  Returns run_es's dict; fval_history / wopt_history hold the stage-local best after
-    every tell (181-185), `stage_wopts` the per-stage optima.  Stage k's CMA-ES is seeded with seed + k."""
-    if distance != "cosine":
+    every tell (181-185), `stage_wopts` the per-stage optima.  Stage k's CMA-ES is seeded with seed + k.
+
+    distance="mrstft": every stage scores its sub-chain's render against the full target AUDIO with an engine.MrstftEvaluator
+    (model and embed_func may be None, nothing is embedded); everything else is as above.  Every stage's sub-chain must
+    render the target's channel count, and savepop is refused as run_es refuses it for this objective."""
+    if distance not in ("cosine", "mrstft"):
         raise ValueError(f"Unknown distance: {distance}")
     savepop = bool(savepop or save_pop)
+    names = list(plugins.keys())
+    if distance == "mrstft":
+        _check_mrstft_staged(input_audio, target_audio, plugins, savepop)
     _, rank, world = _dist_info()
     seed = _agree_on_seed(seed)
     _peak_normalize_(input_audio)
     _peak_normalize_(target_audio)
-    target_embed = embed_func(target_audio, model, sample_rate)
+    target_embed = embed_func(target_audio, model, sample_rate) if distance == "cosine" else None
 
-    names = list(plugins.keys())
     iters_per_stage = max_iters // len(plugins)
     wopt_overall, fopt = None, float("inf")
     fval_history, wopt_history, stage_wopts = [], [], []
@@ -579,7 +613,10 @@ def run_staged_es(
         stage_plugins = {k: plugins[k] for k in names[: stage_idx + 1]}
         print(f"Optimizing stage {stage_idx} ({list(stage_plugins.keys())})")
         n_stage = plugins[names[stage_idx]]["num_params"]
-        evaluator = engine.PopulationEvaluator(input_audio, sample_rate, stage_plugins, model, target_embed, embed_func=embed_func)
+        if distance == "mrstft":
+            evaluator = engine.MrstftEvaluator(input_audio, sample_rate, stage_plugins, target_audio)
+        else:
+            evaluator = engine.PopulationEvaluator(input_audio, sample_rate, stage_plugins, model, target_embed, embed_func=embed_func)
         _chain_dims(evaluator, stage_plugins)
         es = _EsRun.strategy(np.ones(n_stage) * 0.5, sigma0, popsize, None if seed is None else seed + stage_idx)
         for iteration in range(iters_per_stage):
@@ -631,6 +668,7 @@ def run_es_batch(
     random_crop: bool = False,
     seed: int = None,
     early_stop: bool = True,
+    distance: str = "cosine",
 ):
     """ES over B independent (input, target) pairs at once -- BASELINE.json configs[2].
 
@@ -661,12 +699,25 @@ def run_es_batch(
     sharded over the ranks (no collective until the final gather); every rank returns the full list of B result
     dicts.  An unseeded multi-rank
     run agrees on rank 0's draw of a seed first, so that a pair's trajectory does not depend on the rank that owns it (an
-    unseeded run has no defined trajectory anyway, and a single-rank run enters no collective)."""
+    unseeded run has no defined trajectory anyway, and a single-rank run enters no collective).
+
+    distance="mrstft": the objective of run_es(distance="mrstft") -- the multi-resolution STFT distance of the rendered audio to
+    the target AUDIO (engine.MrstftEvaluator); model and embed_func may be None and nothing is embedded.  A target must have
+    its input's length and the chain's output channel count.  Both forms work and keep the promise above, against
+    `run_es(x_b, t_b, ..., None, None, distance="mrstft", find_w0=False, seed=seed + b)`.  In the list form the targets are
+    packed like the inputs (a second engine.RaggedInputs); a length group whose spans can move (random_crop with a member
+    that draws its crops) cuts the active pairs' target crops at the same starts as their inputs, one more gather per
+    iteration, and refills the target table from them; a group whose spans cannot move gathers its targets once, its table
+    is built once, and pairs that stop drop out of it through the slot list of stito_mrstft_loss_slots."""
+    if distance not in ("cosine", "mrstft"):
+        raise ValueError(f"Unknown distance: {distance}")
     ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
     if ragged:
         input_audios, target_audios = _check_ragged_pairs(input_audios, target_audios)
     elif input_audios.dim() != 3 or target_audios.dim() != 3 or input_audios.shape[0] != target_audios.shape[0]:
         raise ValueError("input_audios and target_audios must be (B, chs, seq_len) with the same B")
+    if distance == "mrstft":
+        _check_mrstft_batch(input_audios, target_audios, plugins)
     dist, rank, world = _dist_info()
     seed = _agree_on_seed(seed)
     B_all = len(input_audios)
@@ -680,27 +731,34 @@ def run_es_batch(
             xs, ts = input_audios[lo:hi].clone(), target_audios[lo:hi].clone()
         for a in (*xs, *ts):  # every pair on its own (run_es 452-453); the rows of a tensor are views of the clone
             _peak_normalize_(a)
-        # target embeddings, once: targets of equal shape in one embed_func call
-        by_shape, rows = {}, [None] * len(ts)
-        for b, t in enumerate(ts):
-            by_shape.setdefault(tuple(t.shape), []).append(b)
-        for members in by_shape.values():
-            emb = embed_func(torch.stack([ts[b] for b in members]), model, sample_rate)
-            for k, b in enumerate(members):
-                rows[b] = {name: v.detach().reshape(len(members), -1)[k] for name, v in emb.items()}
-        target_embed = {name: torch.stack([row[name] for row in rows]) for name in rows[0]}
+        if distance == "cosine":
+            # target embeddings, once: targets of equal shape in one embed_func call
+            by_shape, rows = {}, [None] * len(ts)
+            for b, t in enumerate(ts):
+                by_shape.setdefault(tuple(t.shape), []).append(b)
+            for members in by_shape.values():
+                emb = embed_func(torch.stack([ts[b] for b in members]), model, sample_rate)
+                for k, b in enumerate(members):
+                    rows[b] = {name: v.detach().reshape(len(members), -1)[k] for name, v in emb.items()}
+            target_embed = {name: torch.stack([row[name] for row in rows]) for name in rows[0]}
 
         def make_evaluator(x, **kw):
             return engine.PopulationEvaluator(x, sample_rate, plugins, model, target_embed, embed_func=embed_func, **kw)
+
+        def make_mrstft_evaluator(x, y=None):  # the tensor form scores against ts itself, the list form brings its buffers
+            return engine.MrstftEvaluator(x, sample_rate, plugins, ts if y is None else y)
 
         def rng_of(s):  # unseeded: the global generator, not a fresh one
             return np.random if s is None else np.random.RandomState(s)
 
         pair_seeds = [None if seed is None else seed + lo + b for b in range(hi - lo)]  # CMA-ES and, in the list form, crops
-        if ragged:
+        if ragged and distance == "mrstft":
+            evaluator, submit = _ragged_form_mrstft(make_mrstft_evaluator, xs, ts, random_crop, [rng_of(s) for s in pair_seeds])
+        elif ragged:
             evaluator, submit = _ragged_form(make_evaluator, xs, random_crop, [rng_of(s) for s in pair_seeds])
         else:
-            evaluator, submit = _tensor_form(make_evaluator, xs, random_crop, rng_of(seed))
+            evaluator, submit = _tensor_form(make_mrstft_evaluator if distance == "mrstft" else make_evaluator, xs, random_crop,
+                                             rng_of(seed))
         w0 = np.ones(_chain_dims(evaluator, plugins)) * 0.5
         runs = [_EsRun(w0, sigma0, popsize, s) for s in pair_seeds]
         for iteration in range(max_iters):
@@ -732,9 +790,9 @@ def run_es_batch(
 
 
 def _tensor_form(make_evaluator, xs, random_crop, rng):
-    """-> (evaluator, submit) of run_es_batch's tensor form: ALL pairs every iteration, a stopped pair re-submitting its last
-    population -- the input buffer keeps its shape, so the evaluator's graph replay stays eligible -- and one crop position for
-    all, drawn by the evaluator from the one rng."""
+    """-> (evaluator, submit) of run_es_batch's tensor form, for either objective: ALL pairs every iteration, a stopped pair
+    re-submitting its last population -- the input buffer keeps its shape, so the evaluator's graph replay stays eligible -- and
+    one crop position for all (inputs and, under "mrstft", targets alike), drawn by the evaluator from the one rng."""
     evaluator = make_evaluator(xs)
 
     def submit(runs):
@@ -761,6 +819,39 @@ def _ragged_form(make_evaluator, xs, random_crop, rngs):
             starts = [engine.crop_start(ragged.lengths[b], random_crop, rngs[b]) for b in act]
             x = ragged.gather(act, starts, eval_len)
             loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(runs[b].W) for b in act], 0), pairs=act, x=x)
+            pending.append((act, loss))
+        return pending
+
+    return evaluator, submit
+
+
+def _ragged_form_mrstft(make_evaluator, xs, ts, random_crop, rngs):
+    """-> (evaluator, submit) of run_es_batch's list form under distance="mrstft": _ragged_form with a target side.  The targets
+    are packed like the inputs.  A group whose spans can move -- random_crop, and a member long enough to draw its crops -- cuts
+    the active pairs' target crops at the starts of their inputs (one more gather per iteration) and the evaluator refills its
+    table from them.  In any other group every span is [0, eval_len) for good: the targets are gathered once, the table is
+    built once, and pairs that have stopped drop out through the slot list."""
+    device = engine._current_device()
+    ragged, targets = engine.RaggedInputs(xs, device), engine.RaggedInputs(ts, device)
+    # one-sample stand-ins, as in _ragged_form: every call brings its buffers
+    evaluator = make_evaluator(torch.zeros((len(xs), xs[0].shape[0], 1)), torch.zeros((len(ts), ts[0].shape[0], 1)))
+    groups = engine.plan_ragged_groups(ragged.lengths, random_crop)
+    moving = {eval_len: random_crop and any(ragged.lengths[b] - engine.CROP_LEN > engine.CROP_MARGIN for b in members)
+              for eval_len, members in groups}
+    for eval_len, members in groups:
+        if not moving[eval_len]:
+            evaluator.set_static_targets(eval_len, members, targets.gather(members, [0] * len(members), eval_len))
+
+    def submit(runs):
+        pending = []
+        for eval_len, members in groups:  # one or two gathers + one evaluate per group
+            act = [b for b in members if runs[b].active]
+            if not act:
+                continue
+            starts = [engine.crop_start(ragged.lengths[b], random_crop, rngs[b]) for b in act]
+            x = ragged.gather(act, starts, eval_len)
+            y = targets.gather(act, starts, eval_len) if moving[eval_len] else None
+            loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(runs[b].W) for b in act], 0), pairs=act, x=x, y=y)
             pending.append((act, loss))
         return pending
 
