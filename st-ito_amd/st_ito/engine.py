@@ -4,6 +4,10 @@ buffers and the stream.
 
 Reference call sites replaced: the loop `for w in W: process_audio(...)`, the `embed_func` call
 and the cosine loss in run_es.evaluate (st_ito/style_transfer.py:504-573).
+
+The evaluate step exists per objective -- PopulationEvaluator (embeddings, -cosine) and MrstftEvaluator (MRSTFT distance to the
+target audio) -- on one base, _Evaluator, which holds what does not depend on the objective: the compiled chain, the inputs,
+the length policy applied to tensors (eval_span / cut_to_span) and the checks of evaluate's arguments.
 """
 from __future__ import annotations
 
@@ -42,6 +46,30 @@ def eval_length(n: int, random_crop: bool) -> int:
     """Samples per candidate that evaluate renders for an input of n samples: 262144 (zero padded, or cropped), or all n of a
     longer input without random_crop."""
     return CROP_LEN if (random_crop or int(n) <= CROP_LEN) else int(n)
+
+
+def eval_span(n: int, random_crop: bool, rng=np.random, parallel: bool = False) -> Tuple[int, int]:
+    """(start, length) of the samples that one evaluate call reads of an n-sample signal: length == n -- as it is; length < n --
+    the crop [start, start + length); length > n -- zero padded to 262144.  Draws from rng exactly as crop_start does.  The
+    reference's parallel=True branch (499-502) hands the signal to the pool as it is: no padding, no crop, nothing drawn."""
+    if parallel:
+        return 0, int(n)
+    return crop_start(n, random_crop, rng), eval_length(n, random_crop)
+
+
+def cut_to_span(t: torch.Tensor, span: Tuple[int, int], padded: Optional[torch.Tensor] = None):
+    """t (..., n) cut to a span of eval_span -> (t itself (no copy), a contiguous crop, or t zero padded; the padded copy to keep).
+    The caller hands the kept copy back in as `padded`: it is built once, and every call returns the same buffer (a captured
+    graph reads it by address)."""
+    start, length = span
+    n = t.shape[-1]
+    if length == n:
+        return t, padded
+    if length < n:
+        return t[..., start:start + length].contiguous(), padded
+    if padded is None:
+        padded = torch.nn.functional.pad(t, (0, length - n)).contiguous()
+    return padded, padded
 
 
 def plan_ragged_groups(lengths, random_crop: bool) -> List[Tuple[int, List[int]]]:
@@ -277,7 +305,58 @@ def process_audio_gpu(x: np.ndarray, w: np.ndarray, sr: int, plugins: Dict[str, 
 # --------------------------------------------------------------------------------------------
 # population evaluation
 # --------------------------------------------------------------------------------------------
-class PopulationEvaluator:
+class _Evaluator:
+    """What the evaluate step has in common under every objective: the inputs on the device, the compiled chain, the length
+    policy and the checks of evaluate's arguments, each with its one text."""
+
+    def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], device: Optional[torch.device],
+                 normalize_stages: bool):
+        _hip.require_gpu()
+        self.device = device or _current_device()
+        self.sample_rate = sample_rate
+        self.plugins = plugins
+        self.chain = compile_chain(plugins, normalize_stages)
+        self.ndims = self.chain[1]
+        self.n_inputs = x.shape[0]
+        self.x_full = x.to(self.device, torch.float32).contiguous()
+        self._x_padded = None  # cut_to_span's zero-padded copy of x_full
+        self.rendered_candidates = 0
+
+    def _pairs(self, pairs, what: str = "inputs", once: bool = False) -> List[int]:
+        """The listed pairs as ints; `once`: none of them twice."""
+        pairs = [int(b) for b in pairs]
+        if not pairs or (once and len(set(pairs)) != len(pairs)) or any(not 0 <= b < self.n_inputs for b in pairs):
+            raise ValueError(f"pairs {pairs} do not name {what} 0 .. {self.n_inputs - 1}")
+        return pairs
+
+    @staticmethod
+    def _ready_made(t: torch.Tensor, name: str, k: int) -> None:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous() and t.shape[0] == k):
+            raise ValueError(f"{name} must be a contiguous ({k}, chs, n) float32 tensor on the GPU")
+
+    def _arguments(self, W, pairs, x, y=None):
+        """The checks of evaluate(W, pairs=, x=, y=) -> (W as (P, ndims) float64, pairs as ints or None, number of inputs the
+        call reads, candidates per input).  Nothing is drawn and nothing launched before they pass."""
+        Wn = np.asarray(W, dtype=np.float64)
+        if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
+            raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
+        if pairs is not None:
+            pairs = self._pairs(pairs)
+        k = self.n_inputs if pairs is None else len(pairs)
+        if x is not None:
+            self._ready_made(x, "x", k)
+        elif y is not None:
+            raise ValueError("y (ready-made target spans) needs x (the input spans they belong to)")
+        P = Wn.shape[0]
+        if P == 0 or P % k:
+            raise ValueError(f"{P} candidates cannot be split over {k} inputs")
+        return Wn, pairs, k, P // k
+
+    def nan_warning(self) -> Optional[str]:
+        return None
+
+
+class PopulationEvaluator(_Evaluator):
     """GPU replacement of run_es.evaluate (style_transfer.py:474-573) for the AFx-Rep metric.
 
     One instance per run_es call: holds the (padded) input on the device, the compiled chain
@@ -301,18 +380,11 @@ class PopulationEvaluator:
         HBM, handed to embed_func as one (P, C, L) GPU tensor, and every entry of the returned dict is scored against
         the target's entry of the same name.  use_graph: None = STITO_GRAPH (default on), False = eager launches only
         (bench.py's per-launch event timing needs host-side launches)."""
-        _hip.require_gpu()
         from . import utils as _utils
 
-        self.device = device or _current_device()
-        self.sample_rate = sample_rate
-        self.plugins = plugins
-        self.model = model
-        self.chain = compile_chain(plugins, normalize_stages)
-        self.ndims = self.chain[1]
         assert x.dim() == 3, "input audio must be (batch, chs, seq_len)"
-        self.n_inputs = x.shape[0]
-        self.x_full = x.to(self.device, torch.float32).contiguous()
+        super().__init__(x, sample_rate, plugins, device, normalize_stages)
+        self.model = model
         self.embed_func = embed_func
         # the fused path embeds the rendered audio as 48 kHz audio; at any other rate the reference resamples inside
         # get_param_embeds (utils.py:462-463), on both sides of the distance: that goes through the generic path
@@ -351,25 +423,11 @@ class PopulationEvaluator:
         self._graph_calls = {}
         self._graph_evictions = 0
         self._graphs = {}      # (P, input pointer, input shape) -> (graph, W buffer, loss, mid, side, n_calls, buffers kept alive)
-        self._x_padded = None
-        self.rendered_candidates = 0
 
     def _input(self, random_crop: bool, rng, parallel: bool = False) -> torch.Tensor:
-        """Length policy of style_transfer.py:505-518 -- crop_start and eval_length -- with one crop position for all inputs of a
-        batch.  The reference's parallel=True branch (499-502) hands x to the pool as it is: no padding to 262144, no crop, and
-        nothing drawn from rng."""
-        x = self.x_full
-        if parallel:
-            return x
-        n = x.shape[-1]
-        start, length = crop_start(n, random_crop, rng), eval_length(n, random_crop)
-        if length == n:  # a long input without random_crop, or exactly 262144 samples: as it is, no copy
-            return x
-        if length < n:  # cropped, at 0 when no start was drawn
-            return x[..., start:start + length].contiguous()
-        if self._x_padded is None:  # padded once: the same buffer for every call (a captured graph reads it)
-            self._x_padded = torch.nn.functional.pad(x, (0, length - n)).contiguous()
-        return self._x_padded
+        """The evaluator's own input under the length policy (eval_span), with one crop position for all inputs of a batch."""
+        x, self._x_padded = cut_to_span(self.x_full, eval_span(self.x_full.shape[-1], random_crop, rng, parallel), self._x_padded)
+        return x
 
     def _spans(self, p0, p1, per, pairs):
         """-> (inputs of x that candidates p0 .. p1 - 1 read, [(target index, first candidate, end) within the pass])"""
@@ -481,27 +539,13 @@ class PopulationEvaluator:
         x: a ready-made evaluate-time input buffer (len(pairs), C, L) float32 on the device, used as it is -- no padding, no
         crop, nothing drawn from rng; without it the listed pairs are taken from the evaluator's own input by the length policy
         (one crop position for all).  Calls with `pairs` or `x` launch eagerly (no graph replay)."""
-        Wn = np.asarray(W, dtype=np.float64)
-        if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
-            raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
         subset = pairs is not None or x is not None
-        if pairs is not None:
-            pairs = [int(b) for b in pairs]
-            if not pairs or any(not 0 <= b < self.n_inputs for b in pairs):
-                raise ValueError(f"pairs {pairs} do not name inputs 0 .. {self.n_inputs - 1}")
+        Wn, pairs, B, per = self._arguments(W, pairs, x)
         if x is None:
             x = self._input(random_crop, rng, parallel)
             if pairs is not None:
                 x = x[pairs].contiguous()
-        else:
-            n_x = self.n_inputs if pairs is None else len(pairs)
-            if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous() and x.shape[0] == n_x):
-                raise ValueError(f"x must be a contiguous ({n_x}, chs, n) float32 tensor on the GPU")
         P = Wn.shape[0]
-        B = x.shape[0]
-        if P == 0 or P % B:
-            raise ValueError(f"{P} candidates cannot be split over {B} inputs")
-        per = P // B  # candidates per input
         step = min(P, self.max_cand) if self.max_cand else P
         if B > 1:  # passes hold whole pairs
             step = max(per, step // per * per)
@@ -578,18 +622,21 @@ class PopulationEvaluator:
         return None
 
 
-class MrstftEvaluator:
+class MrstftEvaluator(_Evaluator):
     """The evaluate step with the multi-resolution STFT distance to the target AUDIO as the objective (auraloss's
     MultiResolutionSTFTLoss, the reference's second yardstick: scripts/eval/eval_synthetic.py:72, 368-369): render ->
     stito_mrstft_loss with process_audio's joint peak normalisation folded into the kernel's loader.  No model, no embeddings.
 
     x (B, C, n) and target_audio (B, C', n), C' the chain's output channels: candidates of pair b are scored against target b
     (evaluate takes the B populations stacked pair-major, like PopulationEvaluator).  The length policy is the embedding
-    objective's (style_transfer.py:505-518) and the target receives the same span: the same zero padding to 262144, the same
-    crop, and under random_crop the same start -- its table is rebuilt for that crop, one launch sequence on its C' rows.
-    evaluate(W, pairs=[...], x=buffer, y=buffer) scores the populations of a SUBSET of the pairs on ready-made buffers, the
-    counterpart of PopulationEvaluator.evaluate(W, pairs=, x=) -- the ragged batch; `rendered_candidates` counts what went
-    through the render.  Launches are eager."""
+    objective's (eval_span) and ONE span serves input and target alike: the same zero padding to 262144, the same crop, and
+    under random_crop the same start.  evaluate(W, pairs=[...], x=buffer, y=buffer) scores the populations of a SUBSET of the
+    pairs on ready-made buffers, the counterpart of PopulationEvaluator.evaluate(W, pairs=, x=) -- the ragged batch;
+    `rendered_candidates` counts what went through the render.  Launches are eager.
+
+    There are two kinds of target table.  The STATIC table of an evaluate-time length holds ALL the targets, for spans that
+    never move: built once and read through a slot list.  A REFILLED table holds the targets of one call, for spans that move:
+    one per (length, number of targets), rebuilt whenever the spans it holds are not the ones asked for."""
 
     def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor,
                  device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False):
@@ -601,41 +648,15 @@ class MrstftEvaluator:
             raise ValueError(f"target audio {tuple(target_audio.shape)} does not cover the input {tuple(x.shape)}: the MRSTFT "
                              "objective compares sample spans, so batch and length must be equal")
         _features._mrstft_res(resolutions)
-        _hip.require_gpu()
-        self.device = device or _current_device()
-        self.sample_rate = sample_rate
-        self.plugins = plugins
+        super().__init__(x, sample_rate, plugins, device, normalize_stages)
         self.resolutions = resolutions
-        self.chain = compile_chain(plugins, normalize_stages)
-        self.ndims = self.chain[1]
-        self.n_inputs = x.shape[0]
         c_out = _hip.lib().stito_chain_out_channels(self.chain[0], len(plugins), x.shape[1])
         if target_audio.shape[1] != c_out:
             raise ValueError(f"target audio has {target_audio.shape[1]} channels, the chain renders {c_out}")
-        self.x_full = x.to(self.device, torch.float32).contiguous()
         self.y_full = target_audio.to(self.device, torch.float32).contiguous()
-        self._padded = None    # (x, y) zero padded to 262144, built once
-        self._targets = {}     # evaluate-time length -> MrstftTarget of a cropped span (its table is refilled when the crop moves)
-        self._table_span = {}  # evaluate-time length -> the span the table currently holds
-        self._static = {}      # evaluate-time length -> (MrstftTarget of all targets whose spans never move, {pair: slot})
-        self._moving = {}      # (evaluate-time length, number of pairs) -> MrstftTarget that every subset call with y refills
-        self.rendered_candidates = 0
-
-    def _spans(self, random_crop: bool, rng, parallel: bool):
-        """-> (x, y, key of the span): PopulationEvaluator._input's policy applied to input and target alike."""
-        x, y = self.x_full, self.y_full
-        n = x.shape[-1]
-        if parallel:
-            return x, y, ("full",)
-        start, length = crop_start(n, random_crop, rng), eval_length(n, random_crop)
-        if length == n:
-            return x, y, ("full",)
-        if length < n:
-            return x[..., start:start + length].contiguous(), y[..., start:start + length].contiguous(), ("crop", start)
-        if self._padded is None:
-            pad = lambda t: torch.nn.functional.pad(t, (0, length - n)).contiguous()  # noqa: E731
-            self._padded = (pad(x), pad(y))
-        return (*self._padded, ("pad",))
+        self._y_padded = None
+        self._static = {}    # evaluate-time length -> (MrstftTarget of all targets, {pair: slot})
+        self._refilled = {}  # (evaluate-time length, number of targets) -> [MrstftTarget, the spans it holds (None: a caller's y)]
 
     def set_static_targets(self, length: int, pairs, y: torch.Tensor) -> None:
         """The static table of one evaluate-time length, for an evaluator whose own audio is a stand-in (the ragged batch): y
@@ -643,117 +664,88 @@ class MrstftEvaluator:
         once; evaluate(W, pairs=, x=) without y then scores any subset of these pairs through the slot list."""
         from . import features as _features
 
-        pairs = [int(b) for b in pairs]
-        if len(set(pairs)) != len(pairs) or any(not 0 <= b < self.n_inputs for b in pairs):
-            raise ValueError(f"pairs {pairs} do not name targets 0 .. {self.n_inputs - 1}")
+        pairs = self._pairs(pairs, "targets", once=True)
         if y.dim() != 3 or y.shape[0] != len(pairs) or y.shape[-1] != int(length):
             raise ValueError(f"y must be ({len(pairs)}, chs, {int(length)}), got {tuple(y.shape)}")
         self._static[int(length)] = (_features.MrstftTarget(y, self.resolutions), {b: k for k, b in enumerate(pairs)})
 
-    def _static_table(self, length: int, y: Optional[torch.Tensor] = None):
+    def _static_table(self, length: int):
         """-> (MrstftTarget, {pair: slot}) of ALL the targets at an evaluate-time length where no span moves: what
-        set_static_targets registered, else the evaluator's own targets (y, if the caller has them at hand) as they are or zero
-        padded to 262144 (built once)."""
+        set_static_targets registered, else the evaluator's own targets as they are or zero padded to 262144 (built once)."""
         from . import features as _features
 
         ent = self._static.get(length)
         if ent is None:
             n = self.y_full.shape[-1]
-            if y is not None:
-                pass
-            elif length == n:
-                y = self.y_full
-            elif n < length == CROP_LEN:
-                y = torch.nn.functional.pad(self.y_full, (0, length - n)).contiguous()
-            else:
+            if not (length == n or n < length == CROP_LEN):
                 raise ValueError(f"no static targets of {length} samples (the evaluator's own have {n}): pass y")
+            y, self._y_padded = cut_to_span(self.y_full, (0, length), self._y_padded)
             ent = self._static[length] = (_features.MrstftTarget(y, self.resolutions), {b: b for b in range(self.n_inputs)})
         return ent
+
+    def _input_and_target(self, random_crop: bool, rng, parallel: bool = False):
+        """-> (x, y, span): the evaluator's own input and target under the length policy, ONE span (eval_span) for both."""
+        span = eval_span(self.x_full.shape[-1], random_crop, rng, parallel)
+        x, self._x_padded = cut_to_span(self.x_full, span, self._x_padded)
+        y, self._y_padded = cut_to_span(self.y_full, span, self._y_padded)
+        return x, y, span
+
+    def _refilled_table(self, y: torch.Tensor, held):
+        """-> the MrstftTarget of y's shape holding y.  held: what names y's spans from call to call (a table that already holds
+        them is not refilled), or None for a caller's buffer, which always refills."""
+        from . import features as _features
+
+        key = (y.shape[-1], y.shape[0])
+        ent = self._refilled.get(key)
+        if ent is None:
+            ent = self._refilled[key] = [_features.MrstftTarget(y, self.resolutions), held]
+        elif held is None or ent[1] != held:
+            ent[0].update(y)
+            ent[1] = held
+        return ent[0]
 
     def evaluate(self, W, random_crop: bool = False, rng=np.random, want_audio: bool = False, dropout: float = 0.0,
                  parallel: bool = False, pairs=None, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
         """Fitness of every row of W -> (loss (P,), {}, normalised audio or None).
 
-        pairs / x: as PopulationEvaluator.evaluate -- the stacked populations of the listed pairs, in that order, on a
-        ready-made input buffer (len(pairs), C, L) used as it is (nothing drawn from rng); without x the listed pairs are taken
-        from the evaluator's own audio by the length policy.  The target side of a subset call:
+        pairs / x: as PopulationEvaluator.evaluate -- the stacked populations of the listed pairs (default: all), in that order,
+        on a ready-made input buffer (len(pairs), C, L) used as it is (nothing drawn from rng); without x the listed pairs are
+        taken from the evaluator's own audio by the length policy.  The target side:
         y given -- (len(pairs), C', L), the target spans of exactly the listed pairs, for spans that move from call to call:
-            the table is refilled for these len(pairs) targets and population k is scored against target k;
-        y not given -- spans that never move: the table of ALL targets of that length is built once (_static_table) and the
-            subset goes through stito_mrstft_loss_slots, the slot list being the few int32 uploaded per call.  (Without x, a
-            span that the length policy crops is treated as moving: its target crops are taken like the inputs.)"""
-        from . import features as _features
-
+            a refilled table, and population k is scored against target k;
+        x without y -- spans that never move: the static table of that length (_static_table), the listed pairs going through
+            stito_mrstft_loss_slots, the slot list being the few int32 uploaded per call;
+        neither -- the span of the evaluator's own targets that the length policy gave its inputs: a crop is a span that moves
+            (a refilled table, which keeps the crop while the same start is drawn again), anything else is static."""
         if dropout > 0.0:
             raise ValueError("dropout acts on embeddings; the MRSTFT objective has none")
-        Wn = np.asarray(W, dtype=np.float64)
-        if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
-            raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
-        P = Wn.shape[0]
-        if pairs is not None or x is not None or y is not None:
-            return self._evaluate_subset(Wn, random_crop, rng, want_audio, parallel, pairs, x, y)
-        if P == 0 or P % self.n_inputs:
-            raise ValueError(f"{P} candidates cannot be split over {self.n_inputs} inputs")
-        x, y, span = self._spans(random_crop, rng, parallel)
-        length = x.shape[-1]
-        if span[0] != "crop":   # the span never moves: the one static table of this length, shared with the subset calls
-            return self._score(Wn, x, self._static_table(length, y)[0], None, want_audio)
-        tgt = self._targets.get(length)
-        if tgt is None:
-            tgt = self._targets[length] = _features.MrstftTarget(y, self.resolutions)
-        elif self._table_span[length] != span:
-            tgt.update(y)
-        self._table_span[length] = span
-        return self._score(Wn, x, tgt, None, want_audio)
-
-    def _score(self, Wn, x, tgt, slots, want_audio):
-        """render -> loss against the table `tgt` (through the slot list, if there is one)"""
+        subset = pairs is not None or x is not None or y is not None
+        Wn, pairs, k, _ = self._arguments(W, pairs, x, y)
+        held = None
+        if x is None:
+            x, own, span = self._input_and_target(random_crop, rng, parallel)
+            if span[1] < self.y_full.shape[-1]:  # a crop
+                y, held = own, (span, pairs)
+            if pairs is not None:
+                x = x[pairs].contiguous()
+                y = None if y is None else y[pairs].contiguous()
+        elif y is not None:
+            self._ready_made(y, "y", k)
+            if y.shape[-1] != x.shape[-1]:
+                raise ValueError(f"y has {y.shape[-1]} samples, x {x.shape[-1]}")
+        slots = None
+        if y is not None:
+            tgt = self._refilled_table(y, held)
+        else:
+            length = x.shape[-1]
+            tgt, slot_of = self._static_table(length)
+            if subset:
+                pairs = list(range(self.n_inputs)) if pairs is None else pairs
+                if any(b not in slot_of for b in pairs):
+                    raise ValueError(f"pairs {pairs}: the static table of {length} samples holds the targets of {sorted(slot_of)}")
+                slots = torch.tensor([slot_of[b] for b in pairs], dtype=torch.int32).to(self.device)
         Wt = torch.from_numpy(Wn).to(self.device)
-        xin = x[0] if x.shape[0] == 1 else x
-        audio, peaks = render_population(self.plugins, xin, Wt, self.sample_rate, chain=self.chain)
+        audio, peaks = render_population(self.plugins, x[0] if x.shape[0] == 1 else x, Wt, self.sample_rate, chain=self.chain)
         self.rendered_candidates += Wn.shape[0]
         loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots)
         return loss, {}, (normalize_audio_(audio, peaks) if want_audio else None)
-
-    def _evaluate_subset(self, Wn, random_crop, rng, want_audio, parallel, pairs, x, y):
-        from . import features as _features
-
-        pairs = list(range(self.n_inputs)) if pairs is None else [int(b) for b in pairs]
-        if not pairs or any(not 0 <= b < self.n_inputs for b in pairs):
-            raise ValueError(f"pairs {pairs} do not name inputs 0 .. {self.n_inputs - 1}")
-        k, P = len(pairs), Wn.shape[0]
-        if P == 0 or P % k:
-            raise ValueError(f"{P} candidates cannot be split over {k} inputs")
-
-        def ready_made(t, name):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous() and t.shape[0] == k):
-                raise ValueError(f"{name} must be a contiguous ({k}, chs, n) float32 tensor on the GPU")
-
-        if x is None:
-            if y is not None:
-                raise ValueError("y (ready-made target spans) needs x (the input spans they belong to)")
-            xa, ya, span = self._spans(random_crop, rng, parallel)
-            x = xa[pairs].contiguous()
-            if span[0] == "crop":
-                y = ya[pairs].contiguous()
-        else:
-            ready_made(x, "x")
-        length = x.shape[-1]
-        if y is None:   # static spans: the table of all targets, the subset through the slot list
-            tgt, slot_of = self._static_table(length)
-            if any(b not in slot_of for b in pairs):
-                raise ValueError(f"pairs {pairs}: the static table of {length} samples holds the targets of {sorted(slot_of)}")
-            slots = torch.tensor([slot_of[b] for b in pairs], dtype=torch.int32).to(self.device)
-            return self._score(Wn, x, tgt, slots, want_audio)
-        ready_made(y, "y")
-        if y.shape[-1] != length:
-            raise ValueError(f"y has {y.shape[-1]} samples, x {length}")
-        tgt = self._moving.get((length, k))   # moving spans: refilled for exactly these targets, identity map
-        if tgt is None:
-            tgt = self._moving[(length, k)] = _features.MrstftTarget(y, self.resolutions)
-        else:
-            tgt.update(y)
-        return self._score(Wn, x, tgt, None, want_audio)
-
-    def nan_warning(self) -> Optional[str]:
-        return None

@@ -13,7 +13,9 @@ target) pairs optimised together, every iteration evaluating their populations i
 The three ES drivers share one statement of each rule: `_EsRun` is one CMA-ES trajectory with the reference's bookkeeping
 (617-670: pre-tell histories, evaluation count, the stale counter of the early stop) and the result dict; `_agree_on_seed`,
 `_peak_normalize_` and `_chain_dims` are the steps every driver takes before its first iteration.  `run_es` steps one `_EsRun`,
-`run_es_batch` a list of them, `run_staged_es` builds one per stage and keeps run_optim.py's own post-tell histories.
+`run_es_batch` a list of them, `run_staged_es` builds one per stage and keeps run_optim.py's own post-tell histories.  The
+objective (`distance`) is likewise said once for all three: `_check_distance`, `_check_mrstft_pairs` (what distance="mrstft"
+asks of a pair) and `_make_evaluator`, the one place that picks the engine's evaluator; the loops see losses only.
 """
 from __future__ import annotations
 
@@ -400,13 +402,17 @@ def run_es(
     reference is unseeded) and `early_stop` (False disables the break of lines 655-670 for fixed
     work benchmarks).  Under torch.distributed each rank evaluates a contiguous shard of the
     population and the fitness scalars are all-gathered; the CMA-ES state is replicated."""
-    if distance not in ("cosine", "mrstft"):
-        raise ValueError(f"Unknown distance: {distance}")
+    _check_distance(distance)
     if content_model is not None and content_embed_func is None:
         raise ValueError("content_model needs a content_embed_func")
     bs, chs, seq_len = input_audio.shape
     if distance == "mrstft":
-        _check_mrstft_run(input_audio, target_audio, plugins, content_model, dropout, savepop)
+        _check_mrstft_pairs(input_audio, target_audio, plugins, "the target")
+        if content_model is not None:
+            raise ValueError("distance 'mrstft' has no embeddings: content_model cannot be used with it")
+        if dropout > 0:
+            raise ValueError("distance 'mrstft' has no embeddings: dropout must be 0")
+        _check_mrstft_savepop(savepop)
     seed = _agree_on_seed(seed)
     rng = np.random.RandomState(seed) if seed is not None else np.random
 
@@ -414,12 +420,13 @@ def run_es(
     _peak_normalize_(input_audio)
     _peak_normalize_(target_audio)
 
+    options = dict(max_iters=max_iters, w0=w0, find_w0=find_w0, sigma0=sigma0, random_crop=random_crop, popsize=popsize,
+                   parallel=parallel, dropout=dropout, savepop=savepop, run_dir=run_dir, seed=seed, rng=rng, early_stop=early_stop)
     if distance == "mrstft":
         # the objective is the distance to the target AUDIO: no model, no embedding, nothing to compute once but the target's
         # magnitude table, which the evaluator builds for the span it evaluates
-        evaluator = engine.MrstftEvaluator(input_audio, sample_rate, plugins, target_audio)
-        return _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel,
-                        dropout, savepop, run_dir, seed, rng, early_stop, None, "")
+        evaluator = _make_evaluator(distance, input_audio, sample_rate, plugins, None, target_audio)
+        return _es_loop(evaluator, input_audio, sample_rate, plugins, **options)
 
     # compute target embedding (only once)
     target_embed = embed_func(target_audio, model, sample_rate)
@@ -442,58 +449,56 @@ def run_es(
 
     # (run_optim.py:608 passes normalize_stages=...; the reference's run_es swallows it in **kwargs and its evaluate
     # never forwards it to process_audio, so the population is rendered without per-stage normalisation here too)
-    evaluator = engine.PopulationEvaluator(input_audio, sample_rate, plugins, model, eval_targets, embed_func=eval_embed_func,
-                                           entry_weights=entry_weights)
-    return _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel,
-                    dropout, savepop, run_dir, seed, rng, early_stop, content_model, _CP)
+    evaluator = _make_evaluator(distance, input_audio, sample_rate, plugins, model, eval_targets, embed_func=eval_embed_func,
+                                entry_weights=entry_weights)
+    if content_model is not None:  # the reference hands back the style embeddings only (573)
+        with_content = evaluator.evaluate
+
+        def style_only(W, **kw):
+            loss, embeds, audios = with_content(W, **kw)
+            return loss, {k: v for k, v in embeds.items() if not k.startswith(_CP)}, audios
+
+        evaluator.evaluate = style_only
+    return _es_loop(evaluator, input_audio, sample_rate, plugins, **options)
 
 
-def _check_mrstft_run(input_audio, target_audio, plugins, content_model, dropout, savepop):
-    """What run_es(distance="mrstft") cannot do, said before anything is launched."""
-    if target_audio.dim() != 3 or target_audio.shape[0] != input_audio.shape[0] or target_audio.shape[-1] != input_audio.shape[-1]:
-        raise ValueError(f"distance 'mrstft' compares sample spans: the target {tuple(target_audio.shape)} must have the input's "
-                         f"batch and length {tuple(input_audio.shape)}")
-    c_out = engine.chain_out_channels(plugins, input_audio.shape[1])
-    if target_audio.shape[1] != c_out:
-        raise ValueError(f"distance 'mrstft': the target has {target_audio.shape[1]} channels, the chain renders {c_out}")
-    if content_model is not None:
-        raise ValueError("distance 'mrstft' has no embeddings: content_model cannot be used with it")
-    if dropout > 0:
-        raise ValueError("distance 'mrstft' has no embeddings: dropout must be 0")
-    if savepop:
-        raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
+def _check_distance(distance):
+    if distance not in ("cosine", "mrstft"):
+        raise ValueError(f"Unknown distance: {distance}")
 
 
-def _check_mrstft_staged(input_audio, target_audio, plugins, savepop):
-    """What run_staged_es(distance="mrstft") cannot do, said before anything is launched: every stage compares its sub-chain's
-    render with the full target, so every sub-chain has to render the target's channel count."""
-    if target_audio.dim() != 3 or target_audio.shape[0] != input_audio.shape[0] or target_audio.shape[-1] != input_audio.shape[-1]:
-        raise ValueError(f"distance 'mrstft' compares sample spans: the target {tuple(target_audio.shape)} must have the input's "
-                         f"batch and length {tuple(input_audio.shape)}")
-    names = list(plugins.keys())
-    for stage_idx in range(len(names)):
-        c_out = engine.chain_out_channels({k: plugins[k] for k in names[: stage_idx + 1]}, input_audio.shape[1])
-        if c_out != target_audio.shape[1]:
-            raise ValueError(f"distance 'mrstft': stage {stage_idx} ({names[stage_idx]}) renders {c_out} channels, the target has "
-                             f"{target_audio.shape[1]}")
-    if savepop:
-        raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
-
-
-def _check_mrstft_batch(input_audios, target_audios, plugins):
-    """What run_es_batch(distance="mrstft") cannot do, said before anything is launched; both forms (the rows of a (B, chs, n)
-    tensor are its pairs)."""
+def _check_mrstft_pairs(input_audios, target_audios, plugins, target="target {b}", chain="the chain"):
+    """The pair rule of distance="mrstft", said before anything is launched: the distance compares sample spans of the render
+    and of the target, so a target has its input's length and the chain's output channel count.  input_audios / target_audios:
+    lists of (chs, n), or the rows of (B, chs, n) tensors; target / chain: what the messages call the two sides."""
+    if len(target_audios) != len(input_audios):
+        raise ValueError(f"distance 'mrstft': {len(input_audios)} inputs but {len(target_audios)} targets")
     for b, (x, t) in enumerate(zip(input_audios, target_audios)):
-        if t.shape[-1] != x.shape[-1]:
-            raise ValueError(f"distance 'mrstft' compares sample spans: target {b} has {t.shape[-1]} samples, its input {x.shape[-1]}: "
-                             f"the lengths of a pair must be equal")
+        who = target.format(b=b)
+        if t.dim() != 2 or t.shape[-1] != x.shape[-1]:
+            raise ValueError(f"distance 'mrstft' compares sample spans: {who} {tuple(t.shape)} must have the length of its input "
+                             f"{tuple(x.shape)}")
         c_out = engine.chain_out_channels(plugins, x.shape[0])
         if t.shape[0] != c_out:
-            raise ValueError(f"distance 'mrstft': target {b} has {t.shape[0]} channels, the chain renders {c_out}")
+            raise ValueError(f"distance 'mrstft': {who} has {t.shape[0]} channels, {chain} renders {c_out}")
 
 
-def _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel, dropout,
-             savepop, run_dir, seed, rng, early_stop, content_model, _CP):
+def _check_mrstft_savepop(savepop):
+    if savepop:
+        raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
+
+
+def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
+    """The one place that turns `distance` into an evaluator, both resolved through `engine` when called.  target: the target
+    embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft", which
+    embeds nothing and launches eagerly: kw has nothing to say to it)."""
+    if distance == "mrstft":
+        return engine.MrstftEvaluator(x, sample_rate, plugins, target)
+    return engine.PopulationEvaluator(x, sample_rate, plugins, model, target, **kw)
+
+
+def _es_loop(evaluator, input_audio, sample_rate, plugins, *, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel, dropout,
+             savepop, run_dir, seed, rng, early_stop):
     """run_es from its first evaluation on (reference 574-692), for whichever evaluator the distance chose: only losses are
     seen here, so find_w0, the seeded draws, the early stop and the rank sharding are the same for every objective."""
     _, rank, world = _dist_info()
@@ -507,8 +512,6 @@ def _es_loop(evaluator, input_audio, sample_rate, plugins, max_iters, w0, find_w
         warn = evaluator.nan_warning()  # after the fitness download: no extra synchronisation
         if warn:
             print(warn)
-        if content_model is not None:  # the reference hands back the style embeddings only (573)
-            out = (out[0], {k: v for k, v in out[1].items() if not k.startswith(_CP)}, out[2])
         return out
 
     # setup CMA-ES
@@ -592,17 +595,19 @@ def run_staged_es(
     distance="mrstft": every stage scores its sub-chain's render against the full target AUDIO with an engine.MrstftEvaluator
     (model and embed_func may be None, nothing is embedded); everything else is as above.  Every stage's sub-chain must
     render the target's channel count, and savepop is refused as run_es refuses it for this objective."""
-    if distance not in ("cosine", "mrstft"):
-        raise ValueError(f"Unknown distance: {distance}")
+    _check_distance(distance)
     savepop = bool(savepop or save_pop)
     names = list(plugins.keys())
-    if distance == "mrstft":
-        _check_mrstft_staged(input_audio, target_audio, plugins, savepop)
+    if distance == "mrstft":  # every stage compares its sub-chain's render with the full target
+        for stage_idx in range(len(names)):
+            _check_mrstft_pairs(input_audio, target_audio, {k: plugins[k] for k in names[: stage_idx + 1]}, "the target",
+                                f"stage {stage_idx} ({names[stage_idx]})")
+        _check_mrstft_savepop(savepop)
     _, rank, world = _dist_info()
     seed = _agree_on_seed(seed)
     _peak_normalize_(input_audio)
     _peak_normalize_(target_audio)
-    target_embed = embed_func(target_audio, model, sample_rate) if distance == "cosine" else None
+    target = embed_func(target_audio, model, sample_rate) if distance == "cosine" else target_audio
 
     iters_per_stage = max_iters // len(plugins)
     wopt_overall, fopt = None, float("inf")
@@ -613,10 +618,7 @@ def run_staged_es(
         stage_plugins = {k: plugins[k] for k in names[: stage_idx + 1]}
         print(f"Optimizing stage {stage_idx} ({list(stage_plugins.keys())})")
         n_stage = plugins[names[stage_idx]]["num_params"]
-        if distance == "mrstft":
-            evaluator = engine.MrstftEvaluator(input_audio, sample_rate, stage_plugins, target_audio)
-        else:
-            evaluator = engine.PopulationEvaluator(input_audio, sample_rate, stage_plugins, model, target_embed, embed_func=embed_func)
+        evaluator = _make_evaluator(distance, input_audio, sample_rate, stage_plugins, model, target, embed_func=embed_func)
         _chain_dims(evaluator, stage_plugins)
         es = _EsRun.strategy(np.ones(n_stage) * 0.5, sigma0, popsize, None if seed is None else seed + stage_idx)
         for iteration in range(iters_per_stage):
@@ -709,15 +711,14 @@ def run_es_batch(
     that draws its crops) cuts the active pairs' target crops at the same starts as their inputs, one more gather per
     iteration, and refills the target table from them; a group whose spans cannot move gathers its targets once, its table
     is built once, and pairs that stop drop out of it through the slot list of stito_mrstft_loss_slots."""
-    if distance not in ("cosine", "mrstft"):
-        raise ValueError(f"Unknown distance: {distance}")
+    _check_distance(distance)
     ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
     if ragged:
         input_audios, target_audios = _check_ragged_pairs(input_audios, target_audios)
     elif input_audios.dim() != 3 or target_audios.dim() != 3 or input_audios.shape[0] != target_audios.shape[0]:
         raise ValueError("input_audios and target_audios must be (B, chs, seq_len) with the same B")
     if distance == "mrstft":
-        _check_mrstft_batch(input_audios, target_audios, plugins)
+        _check_mrstft_pairs(input_audios, target_audios, plugins)
     dist, rank, world = _dist_info()
     seed = _agree_on_seed(seed)
     B_all = len(input_audios)
@@ -731,6 +732,7 @@ def run_es_batch(
             xs, ts = input_audios[lo:hi].clone(), target_audios[lo:hi].clone()
         for a in (*xs, *ts):  # every pair on its own (run_es 452-453); the rows of a tensor are views of the clone
             _peak_normalize_(a)
+        target = ts  # "mrstft": the audio itself
         if distance == "cosine":
             # target embeddings, once: targets of equal shape in one embed_func call
             by_shape, rows = {}, [None] * len(ts)
@@ -740,25 +742,20 @@ def run_es_batch(
                 emb = embed_func(torch.stack([ts[b] for b in members]), model, sample_rate)
                 for k, b in enumerate(members):
                     rows[b] = {name: v.detach().reshape(len(members), -1)[k] for name, v in emb.items()}
-            target_embed = {name: torch.stack([row[name] for row in rows]) for name in rows[0]}
+            target = {name: torch.stack([row[name] for row in rows]) for name in rows[0]}
 
-        def make_evaluator(x, **kw):
-            return engine.PopulationEvaluator(x, sample_rate, plugins, model, target_embed, embed_func=embed_func, **kw)
-
-        def make_mrstft_evaluator(x, y=None):  # the tensor form scores against ts itself, the list form brings its buffers
-            return engine.MrstftEvaluator(x, sample_rate, plugins, ts if y is None else y)
+        def make_evaluator(x, y=None, **kw):  # y: the list form's stand-in for the target audio (it brings its buffers)
+            return _make_evaluator(distance, x, sample_rate, plugins, model, target if y is None else y, embed_func=embed_func, **kw)
 
         def rng_of(s):  # unseeded: the global generator, not a fresh one
             return np.random if s is None else np.random.RandomState(s)
 
         pair_seeds = [None if seed is None else seed + lo + b for b in range(hi - lo)]  # CMA-ES and, in the list form, crops
-        if ragged and distance == "mrstft":
-            evaluator, submit = _ragged_form_mrstft(make_mrstft_evaluator, xs, ts, random_crop, [rng_of(s) for s in pair_seeds])
-        elif ragged:
-            evaluator, submit = _ragged_form(make_evaluator, xs, random_crop, [rng_of(s) for s in pair_seeds])
+        if ragged:
+            evaluator, submit = _ragged_form(make_evaluator, xs, ts if distance == "mrstft" else None, random_crop,
+                                             [rng_of(s) for s in pair_seeds])
         else:
-            evaluator, submit = _tensor_form(make_mrstft_evaluator if distance == "mrstft" else make_evaluator, xs, random_crop,
-                                             rng_of(seed))
+            evaluator, submit = _tensor_form(make_evaluator, xs, random_crop, rng_of(seed))
         w0 = np.ones(_chain_dims(evaluator, plugins)) * 0.5
         runs = [_EsRun(w0, sigma0, popsize, s) for s in pair_seeds]
         for iteration in range(max_iters):
@@ -802,56 +799,41 @@ def _tensor_form(make_evaluator, xs, random_crop, rng):
     return evaluator, submit
 
 
-def _ragged_form(make_evaluator, xs, random_crop, rngs):
+def _ragged_form(make_evaluator, xs, ts, random_crop, rngs):
     """-> (evaluator, submit) of run_es_batch's list form: per length group the ACTIVE pairs only, each with a crop position of
-    its own from its own rng, cut out of the packed inputs by one gather."""
-    ragged = engine.RaggedInputs(xs, engine._current_device())
-    # the evaluator never reads its own input on this path (every call brings its gathered buffer): a one-sample stand-in
-    evaluator = make_evaluator(torch.zeros((len(xs), xs[0].shape[0], 1)), use_graph=False)
-    groups = engine.plan_ragged_groups(ragged.lengths, random_crop)
+    its own from its own rng, cut out of the packed inputs by one gather.
 
-    def submit(runs):
-        pending = []
-        for eval_len, members in groups:  # one gather + one evaluate per group
-            act = [b for b in members if runs[b].active]
-            if not act:
-                continue
-            starts = [engine.crop_start(ragged.lengths[b], random_crop, rngs[b]) for b in act]
-            x = ragged.gather(act, starts, eval_len)
-            loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(runs[b].W) for b in act], 0), pairs=act, x=x)
-            pending.append((act, loss))
-        return pending
-
-    return evaluator, submit
-
-
-def _ragged_form_mrstft(make_evaluator, xs, ts, random_crop, rngs):
-    """-> (evaluator, submit) of run_es_batch's list form under distance="mrstft": _ragged_form with a target side.  The targets
-    are packed like the inputs.  A group whose spans can move -- random_crop, and a member long enough to draw its crops -- cuts
-    the active pairs' target crops at the starts of their inputs (one more gather per iteration) and the evaluator refills its
-    table from them.  In any other group every span is [0, eval_len) for good: the targets are gathered once, the table is
-    built once, and pairs that have stopped drop out through the slot list."""
+    ts: the target audio, for an objective that compares audio ("mrstft"; None under "cosine"), packed like the inputs.  A group
+    whose spans can move -- random_crop, and a member long enough to draw its crops -- cuts the active pairs' target crops at the
+    starts of their inputs (one more gather per iteration) and the evaluator refills its table from them.  In any other group
+    every span is [0, eval_len) for good: the targets are gathered once, before the first iteration, the table is built once,
+    and pairs that have stopped drop out through the slot list."""
     device = engine._current_device()
-    ragged, targets = engine.RaggedInputs(xs, device), engine.RaggedInputs(ts, device)
-    # one-sample stand-ins, as in _ragged_form: every call brings its buffers
-    evaluator = make_evaluator(torch.zeros((len(xs), xs[0].shape[0], 1)), torch.zeros((len(ts), ts[0].shape[0], 1)))
+    ragged = engine.RaggedInputs(xs, device)
+    targets = None if ts is None else engine.RaggedInputs(ts, device)
+    # the evaluator never reads its own audio on this path (every call brings its gathered buffers): one-sample stand-ins
+    stand_in = lambda audios: torch.zeros((len(audios), audios[0].shape[0], 1))  # noqa: E731
+    evaluator = make_evaluator(stand_in(xs), None if ts is None else stand_in(ts), use_graph=False)
     groups = engine.plan_ragged_groups(ragged.lengths, random_crop)
-    moving = {eval_len: random_crop and any(ragged.lengths[b] - engine.CROP_LEN > engine.CROP_MARGIN for b in members)
-              for eval_len, members in groups}
-    for eval_len, members in groups:
-        if not moving[eval_len]:
-            evaluator.set_static_targets(eval_len, members, targets.gather(members, [0] * len(members), eval_len))
+    moving = set()  # the evaluate-time lengths whose target spans move
+    if targets is not None:
+        for eval_len, members in groups:
+            if random_crop and any(ragged.lengths[b] - engine.CROP_LEN > engine.CROP_MARGIN for b in members):
+                moving.add(eval_len)
+            else:
+                evaluator.set_static_targets(eval_len, members, targets.gather(members, [0] * len(members), eval_len))
 
     def submit(runs):
         pending = []
-        for eval_len, members in groups:  # one or two gathers + one evaluate per group
+        for eval_len, members in groups:  # one gather (two with moving targets) + one evaluate per group
             act = [b for b in members if runs[b].active]
             if not act:
                 continue
             starts = [engine.crop_start(ragged.lengths[b], random_crop, rngs[b]) for b in act]
-            x = ragged.gather(act, starts, eval_len)
-            y = targets.gather(act, starts, eval_len) if moving[eval_len] else None
-            loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(runs[b].W) for b in act], 0), pairs=act, x=x, y=y)
+            buffers = {"x": ragged.gather(act, starts, eval_len)}
+            if eval_len in moving:
+                buffers["y"] = targets.gather(act, starts, eval_len)
+            loss, _, _ = evaluator.evaluate(np.concatenate([np.asarray(runs[b].W) for b in act], 0), pairs=act, **buffers)
             pending.append((act, loss))
         return pending
 
