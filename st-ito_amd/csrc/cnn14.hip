@@ -1261,24 +1261,36 @@ static Cnn14Layer cnn14_layer(const stito_cnn14_weights *w, const int H[7], cons
     return Cnn14Layer{ConvShape{S, H[blk], W[blk], j == 0 ? w->channels[blk] : cout, cout}, pool, (size_t)H[blk + pool] * W[blk + pool] * cout};
 }
 
-// the conv workspace: the largest need among the layers whose algorithm needs one (and conv_block1 in one launch)
+// The launch rule: the kernel conv i runs on the layer l of a device with n_cus CUs, and the weights it runs on.
+// Winograd where a transformed weight set was supplied and the map fits; direct otherwise.  An id that names no Winograd packing
+// means the F(2x2,3x3) one.  (a split packing has no float32 fallback: the direct kernel takes over)
+struct ConvChoice { int algo; const float *w; };
+// n_cus enters through one test, "fewer than 3 / 4 of a six-sweep workgroup per CU": between these two lies every outcome of the rule
+constexpr int64_t CUS_NONE = 0, CUS_WITHOUT_END = INT64_MAX / 4;
+static ConvChoice cnn14_choice(const stito_cnn14_weights *w, int i, const Cnn14Layer &l, int64_t n_cus) {
+    int walgo = conv_algo(w->conv_wino_algo[i]).winograd ? w->conv_wino_algo[i] : STITO_CONV_WINOGRAD;
+    const int same = conv_algo(walgo).same_packing;
+    if (same >= 0 && !l.supported(walgo)) walgo = same;
+    const float *wino_w = w->conv_wino_dev[i];
+    if (walgo == STITO_CONV_WINOGRAD_F4_SPLIT3 && w->conv_alt_dev[i] != nullptr && w->conv_alt_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT2 &&
+        4 * wino43_split3_workgroups(l.c, l.pool != 0) < 3 * n_cus && l.supported(STITO_CONV_WINOGRAD_F4_SPLIT2)) {
+        walgo = STITO_CONV_WINOGRAD_F4_SPLIT2;   // too few of the large workgroups for this batch: the alternative packing
+        wino_w = w->conv_alt_dev[i];
+    }
+    if (wino_w != nullptr && l.supported(walgo)) return ConvChoice{walgo, wino_w};
+    return ConvChoice{STITO_CONV_DIRECT, w->conv_w_dev[i]};
+}
+
+// the conv workspace: the largest need among the layers, each as the launch rule can come out for it -- never the alternative
+// packing (CUS_NONE) or the alternative wherever it covers the shape (CUS_WITHOUT_END) -- and conv_block1 in one launch
 static size_t cnn14_pre_bytes(const stito_cnn14_weights *w, int n_streams, const int H[7], const int W[7]) {
     size_t v = 0;
     for (int i = 0; i < STITO_CNN14_NUM_CONVS; ++i) {
-        const int algo = w->conv_wino_algo[i];
-        if (w->conv_wino_dev[i] == nullptr || !conv_algo(algo).needs_workspace()) continue;
         const Cnn14Layer l = cnn14_layer(w, H, W, i, n_streams);
-        size_t need = l.workspace_bytes(algo);
-        if (w->conv_alt_dev[i] != nullptr) {
-            const size_t alt = l.workspace_bytes(w->conv_alt_algo[i]);
-            need = alt > need ? alt : need;
-        }
-        v = need > v ? need : v;
+        for (const int64_t n_cus : {CUS_NONE, CUS_WITHOUT_END}) v = std::max(v, l.workspace_bytes(cnn14_choice(w, i, l, n_cus).algo));
     }
-    if (w->conv1_f2reg_w_dev != nullptr && w->channels[0] == 1) {   // conv_block1 in one launch: per-stream scales of the log-mel operand
-        const size_t need = stito_conv_block1_f2reg_workspace_bytes(n_streams, H[0], W[0], w->channels[1], w->channels[1], 1);
-        v = need > v ? need : v;
-    }
+    if (w->conv1_f2reg_w_dev != nullptr && w->channels[0] == 1)   // conv_block1 in one launch: per-stream scales of the log-mel operand
+        v = std::max(v, stito_conv_block1_f2reg_workspace_bytes(n_streams, H[0], W[0], w->channels[1], w->channels[1], 1));
     return align_up(v, 256);
 }
 
@@ -1292,10 +1304,6 @@ struct ChunkPlan {
     int first = -1, last = -1, streams = 0;   // first < 0: no chunked run
     size_t scratch_floats = 0;                // per scratch buffer (two of them)
 };
-
-static size_t conv_out_floats_per_stream(const stito_cnn14_weights *w, const int H[7], const int W[7], int i) {
-    return cnn14_layer(w, H, W, i, 1).out_floats;
-}
 
 static ChunkPlan cnn14_chunk_plan(const stito_cnn14_weights *w, int n_streams, const int H[7], const int W[7], bool fuse1r) {
     ChunkPlan p;
@@ -1313,14 +1321,14 @@ static ChunkPlan cnn14_chunk_plan(const stito_cnn14_weights *w, int n_streams, c
     // second); the run's input must not be overwritten by an earlier chunk's output: it is, when both live in actB, unless a
     // stream's output is no larger than its input (chunk c's output then ends before chunk c + 1's input starts)
     if (last % 2 == 1 && first % 2 == 0 && first > 0) {
-        const size_t in_ps = conv_out_floats_per_stream(w, H, W, first - 1), out_ps = conv_out_floats_per_stream(w, H, W, last);
+        const size_t in_ps = cnn14_layer(w, H, W, first - 1, 1).out_floats, out_ps = cnn14_layer(w, H, W, last, 1).out_floats;
         if (out_ps > in_ps) return p;
     }
     if (last % 2 == 0 && first % 2 == 1) return p;  // input and output both in actA (mid-block start): not scheduled
     size_t m = 0;
     for (int i = first; i < last; ++i) {
         if (fuse1r && i == 0) continue;             // never materialised
-        const size_t f = conv_out_floats_per_stream(w, H, W, i);
+        const size_t f = cnn14_layer(w, H, W, i, 1).out_floats;
         m = f > m ? f : m;
     }
     p.first = first; p.last = last; p.streams = sc;
@@ -1451,11 +1459,9 @@ struct Trunk {
 
     unsigned *amax_of(int conv, int s0) const { return (unsigned *)(ws + lay.amax + lay.amax_stride * conv) + s0; }
 
-    // does conv i + 1 run a kernel that scales its transformed input by per-stream maxima of conv i's output?
+    // does conv i + 1, on the same S streams, run a kernel that scales its transformed input by per-stream maxima of conv i's output?
     bool next_wants_amax(int i, int S) const {
-        if (i + 1 >= STITO_CNN14_NUM_CONVS) return false;
-        const int nalgo = w->conv_wino_algo[i + 1];
-        return w->conv_wino_dev[i + 1] != nullptr && conv_algo(nalgo).reads_amax && cnn14_layer(w, H, W, i + 1, S).supported(nalgo);
+        return i + 1 < STITO_CNN14_NUM_CONVS && conv_algo(cnn14_choice(w, i + 1, cnn14_layer(w, H, W, i + 1, S), n_cus).algo).reads_amax;
     }
 
     // conv_block1 as one launch on the register-resident F(2x2,3x3) kernel (it computes the first conv into its patch ring)
@@ -1475,30 +1481,28 @@ struct Trunk {
     // these streams' maxima (buffer of conv i - 1), out -- this launch reported its own
     int conv(int i, const float *in, float *out, int S, int s0, bool &have_amax) const {
         const Cnn14Layer l = cnn14_layer(w, H, W, i, S);
-        // Winograd where a transformed weight set was supplied and the map fits; direct otherwise.  An id that names no Winograd
-        // packing means the F(2x2,3x3) one.  (a split packing has no float32 fallback: the direct kernel takes over)
-        int walgo = conv_algo(w->conv_wino_algo[i]).winograd ? w->conv_wino_algo[i] : STITO_CONV_WINOGRAD;
-        const int same = conv_algo(walgo).same_packing;
-        if (same >= 0 && !l.supported(walgo)) walgo = same;
-        const float *wino_w = w->conv_wino_dev[i];
-        if (walgo == STITO_CONV_WINOGRAD_F4_SPLIT3 && w->conv_alt_dev[i] != nullptr && w->conv_alt_algo[i] == STITO_CONV_WINOGRAD_F4_SPLIT2 &&
-            4 * wino43_split3_workgroups(l.c, l.pool != 0) < 3 * n_cus && l.supported(STITO_CONV_WINOGRAD_F4_SPLIT2)) {
-            walgo = STITO_CONV_WINOGRAD_F4_SPLIT2;   // too few of the large workgroups for this batch: the alternative packing
-            wino_w = w->conv_alt_dev[i];
-        }
-        const bool wino = wino_w != nullptr && l.supported(walgo);
+        const ConvChoice ch = cnn14_choice(w, i, l, n_cus);
         TimedLaunch t((hipStream_t)stream, g_conv_timing.on && l.c.Cin % 8 == 0);
         STITO_TRY(t.begin(i));
-        const int algo_i = wino ? walgo : STITO_CONV_DIRECT;
         // can this layer's kernel report the maxima the next one wants?  (the first conv's own kernel can)
-        unsigned *amax_out = nullptr;
-        if ((conv_algo(algo_i).reports_amax || (l.c.Cin == 1 && !l.pool)) && next_wants_amax(i, S)) amax_out = amax_of(i, s0);
-        const int rc = conv3x3_ws(algo_i, ConvArgs{in, wino ? wino_w : w->conv_w_dev[i], w->bn_scale_dev[i], w->bn_shift_dev[i], out, l.c,
-                                                   l.pool != 0, ws + lay.vbuf, lay.vbytes, (hipStream_t)stream,
-                                                   (have_amax && i > 0) ? amax_of(i - 1, s0) : nullptr, amax_out, g_wino_trace});
+        unsigned *amax_out = (conv_algo(ch.algo).reports_amax || (l.c.Cin == 1 && !l.pool)) && next_wants_amax(i, S) ? amax_of(i, s0) : nullptr;
+        const int rc = conv3x3_ws(ch.algo, ConvArgs{in, ch.w, w->bn_scale_dev[i], w->bn_shift_dev[i], out, l.c, l.pool != 0, ws + lay.vbuf,
+                                                    lay.vbytes, (hipStream_t)stream, (have_amax && i > 0) ? amax_of(i - 1, s0) : nullptr,
+                                                    amax_out, g_wino_trace});
         if (rc) return rc;
         have_amax = amax_out != nullptr;
         return t.end();
+    }
+
+    // one launch from conv k on: conv_block1 whole where it is one launch (k = 0; it writes conv 1's output), conv k otherwise.  It
+    // writes to out_of(index of the conv whose output that is); `in` and k move on to that output and to the conv that reads it
+    template <class OutOf>
+    int step(int &k, const float *&in, OutOf &&out_of, int S, int s0, bool &have_amax) const {
+        const int k_out = k == 0 && lay.fuse1r ? 1 : k;
+        float *out = out_of(k_out);
+        STITO_TRY(k_out != k ? block1(in, out, S, s0, have_amax) : conv(k, in, out, S, s0, have_amax));
+        in = out; k = k_out + 1;
+        return STITO_OK;
     }
 };
 }  // namespace
@@ -1538,25 +1542,17 @@ extern "C" int stito_cnn14_forward(const stito_cnn14_weights *w, const float *lo
     for (int i = 0; i < STITO_CNN14_NUM_CONVS;) {
         if (i == plan.first) {
             // ---- the chunked run: every layer of it on one chunk of streams after the other ----
-            const size_t in_ps = i == 0 ? (size_t)H[0] * W[0] * (w->channels[0] >= 8 ? w->channels[0] : 1) : conv_out_floats_per_stream(w, H, W, i - 1);
-            const size_t out_ps = conv_out_floats_per_stream(w, H, W, plan.last);
+            const size_t in_ps = i == 0 ? (size_t)H[0] * W[0] * (w->channels[0] >= 8 ? w->channels[0] : 1) : cnn14_layer(w, H, W, i - 1, 1).out_floats;
+            const size_t out_ps = cnn14_layer(w, H, W, plan.last, 1).out_floats;
             float *const run_out = home(plan.last);
             bool all_amax = true;
             for (int s0 = 0; s0 < S; s0 += plan.streams) {
                 const int sc = S - s0 < plan.streams ? S - s0 : plan.streams;
                 const float *cin_ptr = cur + (size_t)s0 * in_ps;
                 bool camax = have_amax;
-                int flip = 0;
-                for (int k = plan.first; k <= plan.last;) {
-                    const bool b1 = k == 0 && lay.fuse1r;   // conv_block1's two convs are one launch writing conv 1's output
-                    const int k_out = b1 ? 1 : k;
-                    float *o = k_out == plan.last ? run_out + (size_t)s0 * out_ps : (flip ? chB : chA);
-                    if (b1) STITO_TRY(tr.block1(cin_ptr, o, sc, s0, camax));
-                    else STITO_TRY(tr.conv(k, cin_ptr, o, sc, s0, camax));
-                    cin_ptr = o;
-                    flip ^= 1;
-                    k = k_out + 1;
-                }
+                int flip = 0;   // the maps inside the run: chA, chB, chA, ...
+                auto out_of = [&](int k_out) { return k_out == plan.last ? run_out + (size_t)s0 * out_ps : ((flip ^= 1) ? chA : chB); };
+                for (int k = plan.first; k <= plan.last;) STITO_TRY(tr.step(k, cin_ptr, out_of, sc, s0, camax));
                 all_amax = all_amax && camax;
             }
             have_amax = all_amax;
@@ -1564,15 +1560,7 @@ extern "C" int stito_cnn14_forward(const stito_cnn14_weights *w, const float *lo
             i = plan.last + 1;
             continue;
         }
-        if (i == 0 && lay.fuse1r) {
-            STITO_TRY(tr.block1(cur, actB, S, 0, have_amax));
-            cur = actB;
-            i = 2;
-            continue;
-        }
-        STITO_TRY(tr.conv(i, cur, home(i), S, 0, have_amax));
-        cur = home(i);
-        ++i;
+        STITO_TRY(tr.step(i, cur, home, S, 0, have_amax));
     }
     const int C6 = w->channels[6], E = w->embed_dim;
     hipLaunchKernelGGL(k_head, dim3((C6 + 255) / 256, S), dim3(256), 0, st, cur, feat, H[6], W[6], C6);

@@ -10,6 +10,7 @@ GPU / library is available.
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -58,6 +59,65 @@ def _mel_filterbank(sr: float, n_fft: int, n_mels: int, fmin: float, fmax: float
         w[i] = np.maximum(0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
     w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
     return w.astype(np.float32)
+
+
+def conv_knobs(env=os.environ) -> SimpleNamespace:
+    """The knobs of the packing rule with their defaults; Cnn14 carries them as attributes of the same names,
+    which tests and tools set on a constructed model before its first _ensure()."""
+    return SimpleNamespace(
+        # 3x3 conv algorithm of the trunk: "winograd_f4" (F(4x4,3x3), default), "winograd" (F(2x2,3x3)) or "direct"
+        conv_algo={"direct": _hip.CONV_DIRECT, "winograd": _hip.CONV_WINOGRAD, "winograd_f4": _hip.CONV_WINOGRAD_F4}[
+            env.get("STITO_CONV_ALGO", "winograd_f4")],
+        # F(4x4,3x3) layers with at least this many output channels run with the input transform hoisted into its own
+        # pass (CONV_WINOGRAD_F4_PRE): from 512 up the 8+ workgroups sharing a pixel block stop repeating it (0 = never)
+        conv_pre_min_cout=int(env.get("STITO_CONV_PRE_MIN_COUT", "512")),
+        # ... and, unless STITO_CONV_SPLIT=0, on the f16 matrix pipe with split operands (CONV_WINOGRAD_F4_SPLIT: every f32
+        # operand as f16 hi + lo, three products, f32 accumulation -- as accurate as the f32 pipe, measured) where cin % 64 == 0
+        conv_split=env.get("STITO_CONV_SPLIT", "1") != "0",
+        # from 256 output channels up (measured at 512 streams: 128 -> 256 channels 4.0 -> 3.6 ms, 256 -> 256 6.4 -> 5.7 ms; below,
+        # the transformed input's round trip through HBM costs more than the matrix pipe saves)
+        conv_split_min_cout=int(env.get("STITO_CONV_SPLIT_MIN_COUT", "256")),
+        # ... on 64 x 64 workgroup tiles in two sweeps (CONV_WINOGRAD_F4_SPLIT2) from this many INPUT channels up: its longer
+        # epilogue (two sweeps, the first one's outputs parked in HBM) is repaid by a third fewer bytes per MAC only when the
+        # channel loop is long (measured at 512 streams: 512 -> 512 4.45 -> 4.20 ms, 2048 -> 2048 4.05 -> 3.05; 256 -> 512 2.51 -> 2.66)
+        conv_split2_min_cin=int(env.get("STITO_CONV_SPLIT2_MIN_CIN", "512")),
+        # ... and on 128 x 128 tiles in SIX sweeps (CONV_WINOGRAD_F4_SPLIT3: half the bytes per MAC again; the rows' contributions
+        # meet in a scratch area) from this many input channels up where cout % 512 == 0: measured at 512 streams 512 -> 512
+        # 3.73 -> 3.42 ms, 512 -> 1024 2.04 -> 1.92, 1024 -> 1024 3.02 -> 2.57, 1024 -> 2048 1.73 -> 1.42, 2048 -> 2048 3.02 -> 2.40
+        # (256 -> 512: 2.35 -> 2.85, the channel loop is too short for six epilogues); 0 = never
+        conv_split3_min_cin=int(env.get("STITO_CONV_SPLIT3_MIN_CIN", "512")),
+        # the 64-input-channel layers (conv_block1.conv2, conv_block2.conv1) by Winograd F(2x2,3x3) on the f16 pipe with the
+        # transformed weights resident in registers and the input transform done in registers (CONV_WINOGRAD_F2_REG), unless
+        # STITO_CONV_F2REG=0
+        conv_f2reg=env.get("STITO_CONV_F2REG", "1") != "0",
+        # conv_block1 as ONE launch of that kernel (the first conv computed into its patch ring); STITO_CONV_FUSE1=0: two launches
+        conv_fuse1=env.get("STITO_CONV_FUSE1", "1") != "0")
+
+
+def conv_packing(cin: int, cout: int, k):
+    """What prepare() packs for a cin -> cout layer beside the direct kernel's weights, under the knobs k (a model or conv_knobs()):
+    (Winograd id, or None for "direct only"; id of the alternative packing, or None).  Pure: DESIGN.md 4.2.2 states the rule."""
+    if k.conv_algo == _hip.CONV_DIRECT or cin % 8 != 0 or cout % 64 != 0:
+        return None, None
+    f4_split = k.conv_algo == _hip.CONV_WINOGRAD_F4 and k.conv_split
+    if f4_split and k.conv_f2reg and cin == 64:
+        return _hip.CONV_WINOGRAD_F2_REG, None
+    if f4_split and 0 < k.conv_split_min_cout <= cout and cin % 64 == 0 and cout % 256 == 0 and (cout < 1024 or cout % 512 == 0):
+        if 0 < k.conv_split3_min_cin <= cin and cout % 512 == 0:
+            # small batches (fewer than 3 / 4 of the six-sweep kernel's workgroups per CU: a population of 32 has 32 of them for
+            # conv_block6) run the two-sweep kernel: its packing rides along (stito_cnn14_forward chooses per call)
+            return _hip.CONV_WINOGRAD_F4_SPLIT3, _hip.CONV_WINOGRAD_F4_SPLIT2
+        return (_hip.CONV_WINOGRAD_F4_SPLIT2 if 0 < k.conv_split2_min_cin <= cin else _hip.CONV_WINOGRAD_F4_SPLIT), None
+    if k.conv_algo == _hip.CONV_WINOGRAD_F4 and 0 < k.conv_pre_min_cout <= cout:
+        return _hip.CONV_WINOGRAD_F4_PRE, None
+    return k.conv_algo, None
+
+
+def conv_block1_fused(k, conv1_shape, algo2) -> bool:
+    """conv_block1 in one launch (stito_conv_block1_f2reg), given its first conv's weight shape and the id packed for its second:
+    the first conv is computed on the matrix pipe into the second conv's patch ring, in the slots where the unfused kernel issues
+    its copies; the 64-channel full-resolution map (7.9 GB at 512 streams, written once and read 1.5 times) never exists"""
+    return bool(k.conv_fuse1) and algo2 == _hip.CONV_WINOGRAD_F2_REG and tuple(conv1_shape[:2]) == (64, 1)
 
 
 class _Holder(nn.Module):
@@ -117,33 +177,10 @@ class Cnn14(nn.Module):
         self._packed_key = None
         self._ws = None
         self.max_streams_per_pass = int(os.environ.get("STITO_MAX_STREAMS", "512"))
-        # 3x3 conv algorithm of the trunk: "winograd_f4" (F(4x4,3x3), default), "winograd" (F(2x2,3x3)) or "direct"
-        self.conv_algo = {"direct": _hip.CONV_DIRECT, "winograd": _hip.CONV_WINOGRAD, "winograd_f4": _hip.CONV_WINOGRAD_F4}[
-            os.environ.get("STITO_CONV_ALGO", "winograd_f4")]
-        # F(4x4,3x3) layers with at least this many output channels run with the input transform hoisted into its own
-        # pass (CONV_WINOGRAD_F4_PRE): from 512 up the 8+ workgroups sharing a pixel block stop repeating it (0 = never)
-        self.conv_pre_min_cout = int(os.environ.get("STITO_CONV_PRE_MIN_COUT", "512"))
-        # ... and, unless STITO_CONV_SPLIT=0, on the f16 matrix pipe with split operands (CONV_WINOGRAD_F4_SPLIT: every f32
-        # operand as f16 hi + lo, three products, f32 accumulation -- as accurate as the f32 pipe, measured) where cin % 64 == 0
-        self.conv_split = os.environ.get("STITO_CONV_SPLIT", "1") != "0"
-        # from 256 output channels up (measured at 512 streams: 128 -> 256 channels 4.0 -> 3.6 ms, 256 -> 256 6.4 -> 5.7 ms; below,
-        # the transformed input's round trip through HBM costs more than the matrix pipe saves)
-        self.conv_split_min_cout = int(os.environ.get("STITO_CONV_SPLIT_MIN_COUT", "256"))
-        # ... on 64 x 64 workgroup tiles in two sweeps (CONV_WINOGRAD_F4_SPLIT2) from this many INPUT channels up: its longer
-        # epilogue (two sweeps, the first one's outputs parked in HBM) is repaid by a third fewer bytes per MAC only when the
-        # channel loop is long (measured at 512 streams: 512 -> 512 4.45 -> 4.20 ms, 2048 -> 2048 4.05 -> 3.05; 256 -> 512 2.51 -> 2.66)
-        self.conv_split2_min_cin = int(os.environ.get("STITO_CONV_SPLIT2_MIN_CIN", "512"))
-        # ... and on 128 x 128 tiles in SIX sweeps (CONV_WINOGRAD_F4_SPLIT3: half the bytes per MAC again; the rows' contributions
-        # meet in a scratch area) from this many input channels up where cout % 512 == 0: measured at 512 streams 512 -> 512
-        # 3.73 -> 3.42 ms, 512 -> 1024 2.04 -> 1.92, 1024 -> 1024 3.02 -> 2.57, 1024 -> 2048 1.73 -> 1.42, 2048 -> 2048 3.02 -> 2.40
-        # (256 -> 512: 2.35 -> 2.85, the channel loop is too short for six epilogues); 0 = never
-        self.conv_split3_min_cin = int(os.environ.get("STITO_CONV_SPLIT3_MIN_CIN", "512"))
-        # the 64-input-channel layers (conv_block1.conv2, conv_block2.conv1) by Winograd F(2x2,3x3) on the f16 pipe with the
-        # transformed weights resident in registers and the input transform done in registers (CONV_WINOGRAD_F2_REG), unless
-        # STITO_CONV_F2REG=0
-        self.conv_f2reg = os.environ.get("STITO_CONV_F2REG", "1") != "0"
-        # conv_block1 as ONE launch of that kernel (the first conv computed into its patch ring); STITO_CONV_FUSE1=0: two launches
-        self.conv_fuse1 = os.environ.get("STITO_CONV_FUSE1", "1") != "0"
+        k = conv_knobs()   # the knobs of the packing rule: read in prepare(), so they may be set on the model until then
+        self.conv_algo, self.conv_pre_min_cout, self.conv_f2reg, self.conv_fuse1 = k.conv_algo, k.conv_pre_min_cout, k.conv_f2reg, k.conv_fuse1
+        self.conv_split, self.conv_split_min_cout = k.conv_split, k.conv_split_min_cout
+        self.conv_split2_min_cin, self.conv_split3_min_cin = k.conv_split2_min_cin, k.conv_split3_min_cin
         # depth-first schedule (stito_cnn14_weights.chunk_*, ABI v10): STITO_TRUNK_CHUNK = streams per chunk (0 = layer by layer),
         # STITO_TRUNK_CHUNK_CONVS = "first:last" conv indices of the run (conv_block<b>.conv<j> = 2 (b - 1) + (j - 1))
         self.trunk_chunk = int(os.environ.get("STITO_TRUNK_CHUNK", "0"))
@@ -183,70 +220,51 @@ class Cnn14(nn.Module):
         W = _hip.Cnn14Weights()
         W.embed_dim, W.n_mels = self.embed_dim, self.mel_bins
         W.chunk_streams, (W.chunk_first_conv, W.chunk_last_conv) = self.trunk_chunk, self.trunk_chunk_convs
-        chans = [1, 64, 128, 256, 512, 1024, 2048]
-        for i, c in enumerate(chans):
-            W.channels[i] = c
+
+        def f32(t):
+            keep.append(t.detach().to(torch.float32).contiguous())
+            return keep[-1]
+
+        def pack(w, algo):
+            packed = torch.empty(L.stito_cnn14_packed_conv_floats(*w.shape[:2], algo), dtype=torch.float32, device=dev)
+            _hip.check(L.stito_cnn14_pack_conv(_hip.ptr(w), *w.shape[:2], algo, _hip.ptr(packed), st))
+            keep.append(packed)
+            return packed.data_ptr()
+
+        def fold(bn, n):   # -> (scale, shift) of an eval-mode BatchNorm2d over n channels; 1 and 0 for anything else
+            is_bn = isinstance(bn, nn.BatchNorm2d)
+            args = [_hip.ptr(f32(t)) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)] if is_bn else [None] * 4
+            scale, shift = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+            _hip.check(L.stito_bn_fold(*args, float(bn.eps) if is_bn else 0.0, n, _hip.ptr(scale), _hip.ptr(shift), st))
+            keep.extend((scale, shift))
+            return scale.data_ptr(), shift.data_ptr()
+
+        W.channels[:7] = [1, 64, 128, 256, 512, 1024, 2048]
         for b in range(6):
             blk = getattr(self, f"conv_block{b + 1}")
-            for j, (conv, bn) in enumerate(((blk.conv1, blk.bn1), (blk.conv2, blk.bn2))):
-                w = conv.weight.detach().to(torch.float32).contiguous()
-                cout, cin = w.shape[0], w.shape[1]
-                packed = torch.empty(L.stito_cnn14_packed_conv_floats(cout, cin, _hip.CONV_DIRECT), dtype=torch.float32, device=dev)
-                _hip.check(L.stito_cnn14_pack_conv(_hip.ptr(w), cout, cin, _hip.CONV_DIRECT, _hip.ptr(packed), st))
-                if self.conv_algo != _hip.CONV_DIRECT and cin % 8 == 0 and cout % 64 == 0:
-                    pre = self.conv_algo == _hip.CONV_WINOGRAD_F4 and 0 < self.conv_pre_min_cout <= cout
-                    split = (self.conv_algo == _hip.CONV_WINOGRAD_F4 and self.conv_split and 0 < self.conv_split_min_cout <= cout and
-                             cin % 64 == 0 and cout % 256 == 0 and (cout < 1024 or cout % 512 == 0))
-                    algo = _hip.CONV_WINOGRAD_F4_SPLIT if split else (_hip.CONV_WINOGRAD_F4_PRE if pre else self.conv_algo)
-                    if split and 0 < self.conv_split2_min_cin <= cin:
-                        algo = _hip.CONV_WINOGRAD_F4_SPLIT2
-                    if split and 0 < self.conv_split3_min_cin <= cin and cout % 512 == 0:
-                        algo = _hip.CONV_WINOGRAD_F4_SPLIT3
-                    if self.conv_algo == _hip.CONV_WINOGRAD_F4 and self.conv_split and self.conv_f2reg and cin == 64 and cout % 64 == 0:
-                        algo = _hip.CONV_WINOGRAD_F2_REG
-                    upk = torch.empty(L.stito_cnn14_packed_conv_floats(cout, cin, algo), dtype=torch.float32, device=dev)
-                    _hip.check(L.stito_cnn14_pack_conv(_hip.ptr(w), cout, cin, algo, _hip.ptr(upk), st))
-                    W.conv_wino_dev[2 * b + j] = upk.data_ptr()
-                    W.conv_wino_algo[2 * b + j] = algo
-                    keep.append(upk)
-                    if algo == _hip.CONV_WINOGRAD_F4_SPLIT3:
-                        # small batches (fewer than 3 / 4 of the six-sweep kernel's workgroups per CU: a population of 32 has 32 of
-                        # them for conv_block6) run the two-sweep kernel: its packing rides along (stito_cnn14_forward chooses per call)
-                        alt = torch.empty(L.stito_cnn14_packed_conv_floats(cout, cin, _hip.CONV_WINOGRAD_F4_SPLIT2), dtype=torch.float32, device=dev)
-                        _hip.check(L.stito_cnn14_pack_conv(_hip.ptr(w), cout, cin, _hip.CONV_WINOGRAD_F4_SPLIT2, _hip.ptr(alt), st))
-                        W.conv_alt_dev[2 * b + j] = alt.data_ptr()
-                        W.conv_alt_algo[2 * b + j] = _hip.CONV_WINOGRAD_F4_SPLIT2
-                        keep.append(alt)
-                scale = torch.empty(cout, dtype=torch.float32, device=dev)
-                shift = torch.empty(cout, dtype=torch.float32, device=dev)
-                if isinstance(bn, nn.BatchNorm2d):
-                    args = [t.detach().to(torch.float32).contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-                    _hip.check(L.stito_bn_fold(*[_hip.ptr(t) for t in args], float(bn.eps), cout, _hip.ptr(scale), _hip.ptr(shift), st))
-                    keep += args
-                else:
-                    _hip.check(L.stito_bn_fold(None, None, None, None, 0.0, cout, _hip.ptr(scale), _hip.ptr(shift), st))
-                idx = 2 * b + j
-                W.conv_w_dev[idx], W.bn_scale_dev[idx], W.bn_shift_dev[idx] = packed.data_ptr(), scale.data_ptr(), shift.data_ptr()
-                keep += [w, packed, scale, shift]
-        if (self.conv_fuse1 and int(W.conv_wino_algo[1]) == _hip.CONV_WINOGRAD_F2_REG and W.conv_wino_dev[1] and
-                self.conv_block1.conv1.weight.shape[:2] == (64, 1)):
-            # conv_block1 in one launch (stito_conv_block1_f2reg): the first conv is computed on the matrix pipe into the second
-            # conv's patch ring, in the slots where the unfused kernel issues its copies; the 64-channel full-resolution map
-            # (7.9 GB at 512 streams, written once and read 1.5 times) never exists
-            w1 = self.conv_block1.conv1.weight.detach().to(torch.float32).contiguous()
+            for idx, conv, bn in ((2 * b, blk.conv1, blk.bn1), (2 * b + 1, blk.conv2, blk.bn2)):
+                w = f32(conv.weight)
+                W.conv_w_dev[idx] = pack(w, _hip.CONV_DIRECT)
+                algo, alt = conv_packing(w.shape[1], w.shape[0], self)   # the packing rule
+                if algo is not None:
+                    W.conv_wino_dev[idx], W.conv_wino_algo[idx] = pack(w, algo), algo
+                if alt is not None:
+                    W.conv_alt_dev[idx], W.conv_alt_algo[idx] = pack(w, alt), alt
+                W.bn_scale_dev[idx], W.bn_shift_dev[idx] = fold(bn, w.shape[0])
+        c1 = self.conv_block1.conv1
+        if conv_block1_fused(self, c1.weight.shape, W.conv_wino_algo[1] if W.conv_wino_dev[1] else None):
             fw = torch.empty(L.stito_cnn14_packed_conv1_f2reg_floats(), dtype=torch.float32, device=dev)
-            _hip.check(L.stito_cnn14_pack_conv1_f2reg(_hip.ptr(w1), W.bn_scale_dev[0], W.bn_shift_dev[0], 64, _hip.ptr(fw), st))
+            _hip.check(L.stito_cnn14_pack_conv1_f2reg(_hip.ptr(f32(c1.weight)), W.bn_scale_dev[0], W.bn_shift_dev[0], 64, _hip.ptr(fw), st))
             W.conv1_f2reg_w_dev = fw.data_ptr()
-            keep += [w1, fw]
+            keep.append(fw)
         for name in ("mid", "side"):
             fc = getattr(self, f"fc_{name}")
-            w = fc.weight.detach().to(torch.float32).contiguous()           # (E, 2048)
+            w, b = f32(fc.weight), f32(fc.bias)           # (E, 2048), (E,)
             wt = torch.empty((w.shape[1], w.shape[0]), dtype=torch.float32, device=dev)
             _hip.check(L.stito_transpose(_hip.ptr(w), w.shape[0], w.shape[1], _hip.ptr(wt), st))
-            b = fc.bias.detach().to(torch.float32).contiguous()
             setattr(W, f"fc_{name}_wt_dev", wt.data_ptr())
             setattr(W, f"fc_{name}_b_dev", b.data_ptr())
-            keep += [w, wt, b]
+            keep.append(wt)
 
         # ---- front end tables ---------------------------------------------------------------
         n_fft = self.window_size
@@ -272,13 +290,7 @@ class Cnn14(nn.Module):
         FE.mel_start_dev, FE.mel_len_dev, FE.mel_off_dev, FE.mel_w_dev = ms.data_ptr(), ml.data_ptr(), mo.data_ptr(), mw.data_ptr()
         keep += [win_t, tw_t, ms, ml, mo, mw]
         if self.input_norm == "batchnorm":
-            bn = self.bn0
-            sc = torch.empty(self.mel_bins, dtype=torch.float32, device=dev)
-            sh = torch.empty(self.mel_bins, dtype=torch.float32, device=dev)
-            args = [t.detach().to(torch.float32).contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-            _hip.check(L.stito_bn_fold(*[_hip.ptr(t) for t in args], float(bn.eps), self.mel_bins, _hip.ptr(sc), _hip.ptr(sh), st))
-            FE.bn0_scale_dev, FE.bn0_shift_dev = sc.data_ptr(), sh.data_ptr()
-            keep += args + [sc, sh]
+            FE.bn0_scale_dev, FE.bn0_shift_dev = fold(self.bn0, self.mel_bins)
         self._packed = (W, FE, keep)
         return self._packed
 
