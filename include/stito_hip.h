@@ -110,7 +110,7 @@ int stito_version(void);
  * 10.0 runs unchanged): 1 = stito_gather_crops; 2 = STITO_FX_DASP_EQ, _DASP_COMPRESSOR, _DASP_DISTORTION (kinds 8 - 10 of
  * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits); 3 = stito_barkspectrum_mixed,
  * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan; 4 = stito_mrstft_table_floats, stito_mrstft_target,
- * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots. */
+ * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots; 6 = the device-resident CMA-ES, stito_cmaes_*. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -566,6 +566,55 @@ int stito_embed_loss(float *mid_dev, float *side_dev, int n_cand, int embed_dim,
  * (the reference's mean over the stacked distances).  embed (n_cand, embed_dim), target (embed_dim). */
 int stito_neg_cosine(const float *embed_dev, int n_cand, int embed_dim, const float *target_dev, float weight,
                      int accumulate, float *loss_dev, void *stream);
+
+/* ---- Device-resident CMA-ES (ABI 10.6): st_ito/cmaes.py's CMAEvolutionStrategy, and the run bookkeeping of run_es around it, with
+ * the state on the device.  Same update rule as the host class -- from the same state and the same deviates the two agree to float64
+ * summation order -- but its own random stream, so not the host's trajectory.  2 <= N <= 128, 2 <= popsize <= 1024, anything else
+ * STITO_E_UNSUPPORTED naming the value; 1 <= max_iters <= 2^20.  Every call takes the (N, popsize, max_iters) the state was sized
+ * with: the library keeps nothing per state.
+ *
+ * The state is ONE device allocation of stito_cmaes_state_bytes() bytes, 8-byte words, laid out by one function that the size query,
+ * the kernels and import / export share.  stito_cmaes_state_offsets() writes the word offsets of its fields (18 values, returned count):
+ *   ints, reals, mean, pc, ps, D, best_x, weights, C, B, invsqrtC, genotypes, log_f, log_x, log_disp, persist, n_ints, disp_row
+ * Words [0, persist) are the state proper -- what import and export move -- and the rest is scratch.
+ *   ints   (int64 x n_ints = 17): iterations done, stale, stopped, counteval | countiter, eigeneval, best_evals, N, popsize, mu,
+ *          max_iters, early_stop, seed, told, need_eig, sweeps of the last decomposition, asked (an ask is pending: set by ask,
+ *          cleared by tell; a tell without one returns without storing anything)
+ *   reals  (double x 16): sigma, best_f, cc, cs, c1, cmu, damps, mueff, chiN, lb, ub, al, au, sum of the weights, hsig of the last
+ *          tell, sigma0
+ *   mean, pc, ps, D, best_x (N each), weights (popsize, negative ones included), C, B, invsqrtC (N x N, row-major), the genotypes of
+ *   the last ask (popsize x N; spent by tell), then the per-iteration logs of max_iters rows: log_f / log_x = best-so-far value /
+ *   vector BEFORE the iteration's tell (run_es's fval_history / wopt_history; the vector is meaningless while the value is inf),
+ *   log_disp = disp_row = 8 doubles: countiter, counteval, best f of the iteration, axis ratio, sigma, min std, max std, hsig.
+ * A state whose `stopped` is set (early stop: stale > 10) or that has logged max_iters iterations is FROZEN: ask, tell and eigen return
+ * without storing anything (ask leaves W_dev as it is; stito_cmaes_eigen, the forced decomposition, too), so a run's result does
+ * not depend on how many iterations were enqueued after the freeze.
+ *
+ * ask, tell, eigen and normals enqueue on `stream`, never synchronise and can be captured into a hipGraph once an eager tell (or
+ * eigen) at that N has run -- the first one sets the decomposition kernel's LDS attribute, once per device; init, import, export and status BLOCK on
+ * `stream` (a host copy) and must not be called while it is being captured.  The random deviates of iteration i are a pure function of
+ * (seed, the state's countiter, element index): output `element` of the splitmix64 stream started at mix(mix(seed) ^ iteration), the
+ * two 32-bit halves through the cosine branch of Box-Muller.  The iteration number is read from the state, not passed: a captured
+ * ask / evaluate / tell sequence replays unchanged. */
+int64_t stito_cmaes_state_bytes(int N, int popsize, int64_t max_iters);   /* host only; negative STITO_E_* for unsupported sizes */
+int stito_cmaes_state_offsets(int N, int popsize, int64_t max_iters, int64_t *offsets, int n_offsets);   /* host only */
+/* Weights and constants of CMAEvolutionStrategy.__init__ in float64 on the host, mean = BoundTransform.inverse(x0), C = B = I. */
+int stito_cmaes_init(void *state_dev, int N, int popsize, const double *x0_host, double sigma0, double lb, double ub, uint64_t seed,
+                     int64_t max_iters, int early_stop, void *stream);
+/* z_dev: (popsize, N) standard normals used as they are, or NULL for the state's own stream.  W_dev (popsize, N) float64: the
+ * phenotypes, the layout stito_render_population reads. */
+int stito_cmaes_ask(void *state_dev, int N, int popsize, int64_t max_iters, const double *z_dev, double *W_dev, void *stream);
+/* fitness_dev (popsize,) float32; ranks as np.argsort(kind="stable"): ascending, NaN last, ties in index order.  Two launches: the
+ * update, then the lazy decomposition (which returns at once when the update did not ask for it). */
+int stito_cmaes_tell(void *state_dev, int N, int popsize, int64_t max_iters, const float *fitness_dev, void *stream);
+/* The decomposition of the state's C now, whatever the lazy rule says: cyclic Jacobi warm-started from B; counters untouched. */
+int stito_cmaes_eigen(void *state_dev, int N, int popsize, int64_t max_iters, void *stream);
+int stito_cmaes_export(const void *state_dev, int N, int popsize, int64_t max_iters, int64_t *ints_host, double *reals_host, void *stream);
+int stito_cmaes_import(void *state_dev, int N, int popsize, int64_t max_iters, const int64_t *ints_host, const double *reals_host, void *stream);
+/* status_host[4] = iterations done, stale, stopped, counteval */
+int stito_cmaes_status(const void *state_dev, int64_t *status_host, void *stream);
+/* count deviates of (seed, iteration) from element `first` on: z_dev (doubles) and / or bits_dev (the 64-bit integer stage), either NULL */
+int stito_cmaes_normals(uint64_t seed, int64_t iteration, int64_t first, int64_t count, double *z_dev, uint64_t *bits_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,10 @@ def build_parser():
     parser.add_argument("--objective", type=str, default="embedding", choices=["embedding", "mrstft"],
                         help="embedding: cosine distance of the --metric embeddings (the reference); mrstft: multi-resolution STFT "
                              "distance to the target audio itself (same length as the input; no checkpoint is loaded)")
+    parser.add_argument("--device-es", action="store_true",
+                        help="step the CMA-ES on the GPU (run_es(device_es=True)): same update rule, its own random stream; single "
+                             "rank, no --savepop, not with --staged")
+    parser.add_argument("--sync-every", type=int, default=4, help="with --device-es: iterations enqueued per status read")
     return parser
 
 
@@ -65,6 +69,8 @@ def main(argv=None):
         raise NotImplementedError("--algorithm autodiff (run_optim.py:237-297) is outside this build: ES path only")
     if args.metric != "param":
         raise NotImplementedError("--metric clap needs laion_clap + downloaded weights; only the AFx-Rep metric is built")
+    if args.device_es and args.staged:
+        raise ValueError("--device-es drives run_es only: it cannot be combined with --staged")
     if args.effect_type == "vst" and args.chain is None:
         raise NotImplementedError("--effect-type vst needs pedalboard VST3 hosting; use --effect-type basic")
 
@@ -130,6 +136,7 @@ def main(argv=None):
         distance="mrstft" if args.objective == "mrstft" else "cosine", parallel=args.parallel, dropout=args.dropout, savepop=args.savepop,
         normalize_stages=args.normalize_stages, run_dir=run_dir, seed=args.seed,
         early_stop=not args.no_early_stop,
+        **({"device_es": True, "sync_every": args.sync_every} if args.device_es else {}),   # absent: the call as it always was
     )
     output_audio = result["output_audio"]
     if rank == 0:

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import torch  # noqa: F401  (must be imported first: brings in the process' libamdhip64.so.7)
 
@@ -148,6 +148,17 @@ SIGNATURES = {
     "stito_climb_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int]),
     "stito_climb_step": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the device-resident CMA-ES (ABI 10.6); every call takes (N, popsize, max_iters) after the state
+    "stito_cmaes_state_bytes": (c_int64, [c_int, c_int, c_int64]),
+    "stito_cmaes_state_offsets": (c_int, [c_int, c_int, c_int64, POINTER(c_int64), c_int]),
+    "stito_cmaes_init": (c_int, [c_void_p, c_int, c_int, POINTER(c_double), c_double, c_double, c_double, c_uint64, c_int64, c_int, c_void_p]),
+    "stito_cmaes_ask": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "stito_cmaes_tell": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "stito_cmaes_eigen": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "stito_cmaes_export": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_double), c_void_p]),
+    "stito_cmaes_import": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_double), c_void_p]),
+    "stito_cmaes_status": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
+    "stito_cmaes_normals": (c_int, [c_uint64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 

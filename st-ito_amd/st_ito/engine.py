@@ -336,8 +336,16 @@ class _Evaluator:
 
     def _arguments(self, W, pairs, x, y=None):
         """The checks of evaluate(W, pairs=, x=, y=) -> (W as (P, ndims) float64, pairs as ints or None, number of inputs the
-        call reads, candidates per input).  Nothing is drawn and nothing launched before they pass."""
-        Wn = np.asarray(W, dtype=np.float64)
+        call reads, candidates per input).  Nothing is drawn and nothing launched before they pass.  W as a torch tensor is a
+        population that is already on the device (the device ES's): it is checked like any other, stays where it is and is
+        returned as it is."""
+        if isinstance(W, torch.Tensor):
+            if not (W.is_cuda and W.dtype == torch.float64 and W.is_contiguous()):
+                raise ValueError(f"parameter vectors given as a tensor must be a contiguous (P, {self.ndims}) float64 tensor on the GPU, "
+                                 f"got {W.dtype} on {W.device}")
+            Wn = W
+        else:
+            Wn = np.asarray(W, dtype=np.float64)
         if Wn.ndim != 2 or Wn.shape[1] != self.ndims:
             raise ValueError(f"parameter vectors must be (P, {self.ndims}), got {tuple(Wn.shape)}")
         if pairs is not None:
@@ -352,7 +360,16 @@ class _Evaluator:
             raise ValueError(f"{P} candidates cannot be split over {k} inputs")
         return Wn, pairs, k, P // k
 
-    def nan_warning(self) -> Optional[str]:
+    def _on_device(self, Wn) -> torch.Tensor:
+        """_arguments' W on the device: a numpy population is uploaded, a device population is used where it is."""
+        return Wn.to(self.device) if isinstance(Wn, torch.Tensor) else torch.from_numpy(Wn).to(self.device)
+
+    def nan_flags(self) -> Optional[torch.Tensor]:
+        """The NaN flags of the last evaluate() as a device tensor, without a synchronisation (None: this objective has none).  A
+        caller that does not fetch every fitness -- the device ES -- adds them up and hands the sum to nan_warning()."""
+        return None
+
+    def nan_warning(self, flags: Optional[torch.Tensor] = None) -> Optional[str]:
         return None
 
 
@@ -464,7 +481,7 @@ class PopulationEvaluator(_Evaluator):
                                           _hip.ptr(self.flags[255]), _hip.stream_ptr()))
         return loss, mid, side, (normalize_audio_(audio, peaks) if want_audio else None), (audio, peaks), n_calls
 
-    def _evaluate_graph(self, Wn: np.ndarray, x, per):
+    def _evaluate_graph(self, Wn, x, per):
         """The plain fused call as one hipGraph launch, or None while this (population size, input buffer) has been seen fewer than
         capture_after times.  W travels through a static device buffer; the outputs are copied out of the graph's buffers, so
         they stay valid across calls."""
@@ -479,7 +496,7 @@ class PopulationEvaluator(_Evaluator):
             if len(self._graphs) >= 4 and self._graph_evictions >= 8:
                 return None   # more than four shapes keep rotating: every call would re-capture (10 - 30 ms each); stay eager
             Wbuf = torch.empty((P, self.ndims), dtype=torch.float64, device=self.device)
-            Wbuf.copy_(torch.from_numpy(Wn))
+            Wbuf.copy_(Wn if isinstance(Wn, torch.Tensor) else torch.from_numpy(Wn))
             if seen == 0:
                 # nothing of this shape has run yet: one eager pass first (not part of the graph), which builds everything lazy
                 # -- packed weights, workspaces, LDS attributes -- outside the capture
@@ -523,7 +540,7 @@ class PopulationEvaluator(_Evaluator):
                 self._graph_evictions += 1
             self._graphs[key] = ent
         g, Wbuf, loss, mid, side, n_calls, _ = ent
-        Wbuf.copy_(torch.from_numpy(Wn))
+        Wbuf.copy_(Wn if isinstance(Wn, torch.Tensor) else torch.from_numpy(Wn))   # a device population: device to device
         g.replay()
         self.rendered_candidates += P
         self._n_flag_rows = min(n_calls, 255)
@@ -557,7 +574,7 @@ class PopulationEvaluator(_Evaluator):
             out = self._evaluate_graph(Wn, x, per)
             if out is not None:
                 return out
-        Wt = torch.from_numpy(Wn).to(self.device)
+        Wt = self._on_device(Wn)
         losses, mids, sides, audios, generic_embeds = [], [], [], [], []
         n_calls = 0
         for p0, p1 in bounds:
@@ -611,10 +628,14 @@ class PopulationEvaluator(_Evaluator):
                                               0 if idx == 0 else 1, _hip.ptr(loss[q0:q1]), _hip.stream_ptr()))
         return loss, out
 
-    def nan_warning(self) -> Optional[str]:
-        """The reference's "Warning: NaNs found in ..._embeddings" (utils.py:491-497) for the last evaluate();
-        reads the device flags, so call it after the fitness has been fetched (run_es does)."""
-        fl = self.flags[: getattr(self, "_n_flag_rows", 0)].sum(dim=0).cpu()
+    def nan_flags(self) -> Optional[torch.Tensor]:
+        return self.flags[: getattr(self, "_n_flag_rows", 0)].sum(dim=0)
+
+    def nan_warning(self, flags: Optional[torch.Tensor] = None) -> Optional[str]:
+        """The reference's "Warning: NaNs found in ..._embeddings" (utils.py:491-497) for the last evaluate() -- or for the
+        evaluate() calls whose nan_flags() were added up into `flags`; reads the device flags, so call it after the fitness
+        has been fetched (run_es does)."""
+        fl = (self.nan_flags() if flags is None else flags).cpu()
         if fl.numel() and int(fl[0]):
             return "Warning: NaNs found in mid_embeddings"
         if fl.numel() and int(fl[1]):
@@ -744,7 +765,7 @@ class MrstftEvaluator(_Evaluator):
                 if any(b not in slot_of for b in pairs):
                     raise ValueError(f"pairs {pairs}: the static table of {length} samples holds the targets of {sorted(slot_of)}")
                 slots = torch.tensor([slot_of[b] for b in pairs], dtype=torch.int32).to(self.device)
-        Wt = torch.from_numpy(Wn).to(self.device)
+        Wt = self._on_device(Wn)
         audio, peaks = render_population(self.plugins, x[0] if x.shape[0] == 1 else x, Wt, self.sample_rate, chain=self.chain)
         self.rendered_candidates += Wn.shape[0]
         loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots)

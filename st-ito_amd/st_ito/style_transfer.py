@@ -391,6 +391,8 @@ def run_es(
     run_dir: str = ".",
     seed: int = None,
     early_stop: bool = True,
+    device_es: bool = False,
+    sync_every: int = 4,
     *args,
     **kwargs,
 ):
@@ -401,8 +403,16 @@ def run_es(
     262144 samples, no random crop); the whole population is rendered on the GPU at once either way.  Extensions: `seed` (CMA-ES + find_w0 RNG; the
     reference is unseeded) and `early_stop` (False disables the break of lines 655-670 for fixed
     work benchmarks).  Under torch.distributed each rank evaluates a contiguous shard of the
-    population and the fitness scalars are all-gathered; the CMA-ES state is replicated."""
+    population and the fitness scalars are all-gathered; the CMA-ES state is replicated.
+
+    device_es=True steps the CMA-ES on the GPU (cmaes.DeviceCMAEvolutionStrategy): ask -> evaluate -> tell are enqueued `sync_every`
+    iterations at a time and the host reads one status record per batch, where it also prints the iterations' disp lines.  Same
+    update rule, the library's own random stream: NOT the trajectory the host ES walks from the same seed.  Single rank only and no
+    savepop; max_iters must be at least 1 (the host ES accepts 0); find_w0 is the host-drawn population it always was.  NaN
+    warnings are printed once per batch, for all of its passes."""
     _check_distance(distance)
+    if device_es:
+        _check_device_es(plugins, popsize, max_iters, savepop, sync_every)
     if content_model is not None and content_embed_func is None:
         raise ValueError("content_model needs a content_embed_func")
     bs, chs, seq_len = input_audio.shape
@@ -421,7 +431,8 @@ def run_es(
     _peak_normalize_(target_audio)
 
     options = dict(max_iters=max_iters, w0=w0, find_w0=find_w0, sigma0=sigma0, random_crop=random_crop, popsize=popsize,
-                   parallel=parallel, dropout=dropout, savepop=savepop, run_dir=run_dir, seed=seed, rng=rng, early_stop=early_stop)
+                   parallel=parallel, dropout=dropout, savepop=savepop, run_dir=run_dir, seed=seed, rng=rng, early_stop=early_stop,
+                   device_es=device_es, sync_every=sync_every)
     if distance == "mrstft":
         # the objective is the distance to the target AUDIO: no model, no embedding, nothing to compute once but the target's
         # magnitude table, which the evaluator builds for the span it evaluates
@@ -462,6 +473,19 @@ def run_es(
     return _es_loop(evaluator, input_audio, sample_rate, plugins, **options)
 
 
+def _check_device_es(plugins, popsize, max_iters, savepop, sync_every):
+    """What run_es(device_es=True) refuses, said before an input is normalised or anything launched."""
+    if _dist_info()[2] > 1:
+        raise ValueError("device_es steps ONE CMA-ES state on one GPU: it cannot run under a torch.distributed world larger than 1")
+    if savepop:
+        raise ValueError("device_es keeps the populations on the device: savepop is not supported")
+    if int(sync_every) < 1:
+        raise ValueError(f"sync_every must be at least 1, got {sync_every}")
+    if int(max_iters) < 1:
+        raise ValueError(f"device_es logs its iterations in a state sized by max_iters: it must be at least 1, got {max_iters}")
+    cma.device_es_state_bytes(sum(plugin["num_params"] for plugin in plugins.values()), popsize, max_iters)
+
+
 def _check_distance(distance):
     if distance not in ("cosine", "mrstft"):
         raise ValueError(f"Unknown distance: {distance}")
@@ -498,7 +522,7 @@ def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
 
 
 def _es_loop(evaluator, input_audio, sample_rate, plugins, *, max_iters, w0, find_w0, sigma0, random_crop, popsize, parallel, dropout,
-             savepop, run_dir, seed, rng, early_stop):
+             savepop, run_dir, seed, rng, early_stop, device_es=False, sync_every=4):
     """run_es from its first evaluation on (reference 574-692), for whichever evaluator the distance chose: only losses are
     seen here, so find_w0, the seeded draws, the early stop and the rank sharding are the same for every objective."""
     _, rank, world = _dist_info()
@@ -533,6 +557,11 @@ def _es_loop(evaluator, input_audio, sample_rate, plugins, *, max_iters, w0, fin
     init_param_dict = parameters_to_dict(w0, plugins)
     print(init_param_dict)
 
+    if device_es:
+        return _device_es_iterations(evaluator, input_audio, sample_rate, plugins, w0, popsize if find_w0 else 0, max_iters=max_iters,
+                                     sigma0=sigma0, random_crop=random_crop, popsize=popsize, parallel=parallel, dropout=dropout,
+                                     seed=seed, rng=rng, early_stop=early_stop, sync_every=sync_every)
+
     run = _EsRun(w0, sigma0, popsize, seed)
     run.n_evals = popsize if find_w0 else 0
 
@@ -556,6 +585,48 @@ def _es_loop(evaluator, input_audio, sample_rate, plugins, *, max_iters, w0, fin
     # render the current solution on the full (un-padded) input, like the reference (676-678)
     output_audio = torch.from_numpy(process_audio(input_audio.squeeze(0).cpu().numpy(), run.es.result[0], sample_rate, plugins))
     return run.result(output_audio, plugins)
+
+
+def _device_es_iterations(evaluator, input_audio, sample_rate, plugins, w0, n_evals, *, max_iters, sigma0, random_crop, popsize, parallel,
+                          dropout, seed, rng, early_stop, sync_every):
+    """_es_loop's iterations with the strategy on the device: nothing crosses to the host inside a batch of `sync_every`
+    iterations -- the population goes from ask to the evaluator and the loss to tell as device tensors -- and the state freezes
+    itself at the early stop, so iterations enqueued after it change nothing and the result does not depend on sync_every."""
+    opts = {"bounds": [0, 1], "popsize": popsize}
+    if seed is not None:
+        opts["seed"] = seed
+    es = cma.DeviceCMAEvolutionStrategy(w0, sigma0, opts, max_iters=max_iters, early_stop=early_stop)
+    enqueued = shown = n_stale = 0
+    while enqueued < max_iters:
+        flags = None   # the NaN flags of the batch's passes, added up on the device: one warning per batch, none lost
+        for _ in range(min(int(sync_every), max_iters - enqueued)):
+            W = es.ask_device()
+            loss, _, _ = evaluator.evaluate(W, random_crop=random_crop, rng=rng, want_audio=False,
+                                            dropout=(dropout if (enqueued + 1) < max_iters else 0.0), parallel=parallel)
+            es.tell_device(loss)
+            enqueued += 1
+            fl = evaluator.nan_flags()
+            flags = fl if flags is None or fl is None else flags + fl
+        status = es.status()
+        warn = evaluator.nan_warning(flags) if flags is not None else None
+        if warn:
+            print(warn)
+        before, rows = es.log_rows(shown, status["iterations"])
+        for i, (line, f_before, f_it) in enumerate(zip(es.disp_lines(rows=rows), before, rows[:, 2]), start=shown):
+            print(line)
+            stale = i > 0 and f_it - f_before > -0.01
+            n_stale = n_stale + 1 if stale else 0
+            if stale:
+                print(f"Solution has not improved for {n_stale} iterations.")
+        shown = status["iterations"]
+        if status["stopped"]:
+            print("Stopping early due to no improvement.")
+            break
+    state = es.export()
+    fval_history, wopt_history = es.logs(state)
+    wopt, fopt = (state["best_x"] if state["best_f"] < float("inf") else None), state["best_f"]
+    output_audio = torch.from_numpy(process_audio(input_audio.squeeze(0).cpu().numpy(), wopt, sample_rate, plugins))
+    return _es_result(output_audio, wopt, fopt, fval_history, wopt_history, n_evals + state["done"] * popsize, plugins)
 
 
 def run_staged_es(
