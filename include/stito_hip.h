@@ -110,7 +110,8 @@ int stito_version(void);
  * 10.0 runs unchanged): 1 = stito_gather_crops; 2 = STITO_FX_DASP_EQ, _DASP_COMPRESSOR, _DASP_DISTORTION (kinds 8 - 10 of
  * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits); 3 = stito_barkspectrum_mixed,
  * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan; 4 = stito_mrstft_table_floats, stito_mrstft_target,
- * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots; 6 = the device-resident CMA-ES, stito_cmaes_*. */
+ * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots; 6 = the device-resident CMA-ES, stito_cmaes_*;
+ * 7 = stito_mrstft_target_sd, stito_mrstft_loss_sd, stito_mrstft_loss_slots_sd. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -540,7 +541,19 @@ int stito_gather_crops(const float *packed_dev, int64_t packed_floats, const int
  * NaN for that population's losses, reads nothing from the table and leaves the other populations' bits as they are (the contract
  * of stito_gather_crops for a slot that names no pair).  Workspace: stito_mrstft_workspace_bytes(pop, ...), as before.  Same
  * kernels, same fixed-order sums: a candidate's loss has the same bits under every slot list as under stito_mrstft_loss on a table
- * that holds only its target, and stito_mrstft_loss is this call with the identity map (n_slots = n_targets, slot k = k). */
+ * that holds only its target, and stito_mrstft_loss is this call with the identity map (n_slots = n_targets, slot k = k).
+ *
+ * The sum / difference variants (ABI 10.7): auraloss.freq.SumAndDifferenceSTFTLoss with both weights 1 (restated, PARITY UNPINNED) --
+ * the distance above of the 2-channel signal [ch0 + ch1, ch0 - ch1] of every item, no factor 1/2: an item's loss is the mean over
+ * resolutions of the mean over the two rows {sum, difference} of sc + lm.  stito_mrstft_target_sd: y_dev (n_targets, 2, n_samples)
+ * -> a table of 2 n_targets rows (stito_mrstft_table_floats(res, n_res, 2 * n_targets, n_samples) floats), row 2 t the sum row and
+ * row 2 t + 1 the difference row of target t.  stito_mrstft_loss_sd / stito_mrstft_loss_slots_sd: stito_mrstft_loss /
+ * stito_mrstft_loss_slots against such a table, every argument as there (workspace: stito_mrstft_workspace_bytes(pop, 2, ...)); the
+ * loader reads both channels of a candidate and forms xL r + xR r, respectively xL r - xR r (r = 1 / clip(peaks_dev[p], 1e-8) under
+ * norm_passes 1, else 1; two products and one add).  Everything behind the loader is the code above, so the same promises hold:
+ * fixed-order sums, the same bits at every position of every batch and under every slot list, loss(y, table_sd(y)) exactly 0, NaN
+ * for a slot that names no target.  channels must be 2: anything else is STITO_E_INVALID.  A table and the loss scored against it
+ * must be of the same kind; the table does not record which. */
 int64_t stito_mrstft_table_floats(const int *res, int n_res, int rows, int64_t n_samples);
 int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev, void *stream);
 size_t stito_mrstft_workspace_bytes(const int *res, int n_res, int pop, int channels, int64_t n_samples);
@@ -551,6 +564,15 @@ int stito_mrstft_loss_slots(const int *res, int n_res, const float *audio_dev, c
                             const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
                             int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
                             void *stream);
+int stito_mrstft_target_sd(const int *res, int n_res, const float *y_dev, int n_targets, int channels, int64_t n_samples,
+                           float *table_dev, void *stream);
+int stito_mrstft_loss_sd(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                         const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+int stito_mrstft_loss_slots_sd(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                               const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
+                               int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
+                               void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

@@ -19,6 +19,11 @@
 // one function compiled without fp contraction (Makefile), so loss(y, table(y)) is exactly 0.  Sums: per lane in float64,
 // per tile a fixed-order tree in LDS, per-tile partials to the workspace, one small launch adds the tiles in order -- no
 // atomics, and a candidate's loss depends on nothing but its own audio, its target and the resolutions.
+//
+// The sum / difference variant (template SD; auraloss.freq.SumAndDifferenceSTFTLoss with both weights 1, restated) is the same
+// distance of the 2-channel signal [L + R, L - R], no factor 1/2: only the loader differs.  Row 2 item is the sum row and row
+// 2 item + 1 the difference row; the workgroup reads the span of BOTH channels of its item and stores xL r1 + xR r1, respectively
+// xL r1 - xR r1 (two products and one add, uncontracted).  Table, workspace and everything behind the span are those of C = 2.
 #include "common.h"
 
 namespace stito {
@@ -191,7 +196,8 @@ __device__ __forceinline__ int mr_target_of(int64_t cand, int per_target, const 
 // else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row mr_target_of(cand) * C + ch;
 //         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).  A candidate whose slot names no target
 //         reads nothing from the table and writes no partial: k_mrstft_final gives it NaN.
-template <bool TARGET>
+// SD:     C = 2 and audio = (items, 2, n) on both sides; row 2 item + 0 is the item's L + R, row 2 item + 1 its L - R.
+template <bool TARGET, bool SD>
 __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__restrict__ audio, const float *__restrict__ peaks,
                                                       int norm_passes, int C, int per_target, const int32_t *__restrict__ slots,
                                                       int n_targets) {
@@ -218,7 +224,7 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__r
         if (peaks != nullptr && norm_passes > 0) r1 = 1.0f / fmaxf(peaks[cand], 1e-8f);  // x * (1 / d), as stito_logmel
         trow = (int64_t)t * C + (row - cand * C);
     }
-    const float *x = audio + row * d.n;
+    const float *x = audio + (SD ? (row & ~(int64_t)1) : row) * d.n;  // SD: the item's channel 0; channel 1 lies behind it
 
     for (int i = tid; i < N2; i += MR_THREADS) tw_s[i] = d.tw[i];
     for (int i = tid; i < N; i += MR_THREADS) win_s[i] = d.win[i];
@@ -229,7 +235,12 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__r
         int64_t s = s0 + i;
         if (s < 0) s = -s;
         if (s >= d.n) s = 2 * (d.n - 1) - s;
-        span[i] = x[s] * r1;
+        if (SD) {
+            const float l = x[s] * r1, r = x[d.n + s] * r1;
+            span[i] = (row & 1) ? l - r : l + r;
+        } else {
+            span[i] = x[s] * r1;
+        }
     }
     __syncthreads();
 
@@ -378,24 +389,32 @@ extern "C" size_t stito_mrstft_workspace_bytes(const int *res, int n_res, int po
     return (size_t)pop * channels * p.tiles_total * 2 * sizeof(double);
 }
 
-extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
-                                   void *stream) {
+// The sum / difference variant takes 2-channel items only: its rows are an item's L + R and L - R.
+static int mr_sd_channels(const char *who, int channels) {
+    STITO_REQUIRE(channels == 2, STITO_E_INVALID, "%s: the sum / difference distance needs 2 channels, got %d", who, channels);
+    return STITO_OK;
+}
+
+// The one launch path of the table.  SD: y_dev is (rows / 2, 2, n) and row 2 t + 0 / 1 of the table is target t's L + R / L - R.
+template <bool SD>
+static int mr_target(const char *who, const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
+                     void *stream) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
     STITO_TRY(mr_plan(res, n_res, n_samples, p));
     STITO_TRY(mr_device_fits(p));
-    STITO_REQUIRE(rows >= 1, STITO_E_INVALID, "stito_mrstft_target: %d rows", rows);
-    STITO_REQUIRE(y_dev != nullptr && table_dev != nullptr, STITO_E_INVALID, "stito_mrstft_target: null pointer");
-    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "stito_mrstft_target: the table must be 16-byte aligned");
+    STITO_REQUIRE(rows >= 1, STITO_E_INVALID, "%s: %d rows", who, rows);
+    STITO_REQUIRE(y_dev != nullptr && table_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);
+    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "%s: the table must be 16-byte aligned", who);
     double *sums = (double *)(table_dev + p.mags_base + (int64_t)rows * p.row_floats);
     double *partial = sums + (int64_t)rows * p.n_res;
     for (int i = 0; i < p.n_res; ++i) {
-        STITO_REQUIRE((int64_t)rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "stito_mrstft_target: too many tiles");
+        STITO_REQUIRE((int64_t)rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "%s: too many tiles", who);
         const MrDev d = mr_dev(p, i, n_samples, table_dev, partial, 1);
         hipLaunchKernelGGL(k_mrstft_tables, dim3((d.N + 255) / 256), dim3(256), 0, st, (float2 *)d.tw, (float *)d.win, d.N, p.win[i]);
         STITO_LAUNCH_CHECK();
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
-        hipLaunchKernelGGL(k_mrstft<true>, dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true, SD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL((k_mrstft<true, SD>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
                            (const float *)nullptr, 0, 1, 1, (const int32_t *)nullptr, rows);
         STITO_LAUNCH_CHECK();
     }
@@ -405,8 +424,21 @@ extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev
     return STITO_OK;
 }
 
+extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
+                                   void *stream) {
+    return mr_target<false>("stito_mrstft_target", res, n_res, y_dev, rows, n_samples, table_dev, stream);
+}
+
+extern "C" int stito_mrstft_target_sd(const int *res, int n_res, const float *y_dev, int n_targets, int channels, int64_t n_samples,
+                                      float *table_dev, void *stream) {
+    STITO_TRY(mr_sd_channels("stito_mrstft_target_sd", channels));
+    STITO_REQUIRE(n_targets >= 1 && n_targets < (1 << 30), STITO_E_INVALID, "stito_mrstft_target_sd: %d targets", n_targets);
+    return mr_target<true>("stito_mrstft_target_sd", res, n_res, y_dev, 2 * n_targets, n_samples, table_dev, stream);
+}
+
 // The one launch path of the loss: populations of pop / n_slots candidates, population k against target target_slot[k] of the
 // table's n_targets, or against target k when there is no slot list (then n_slots == n_targets).
+template <bool SD>
 static int mr_loss(const char *who, const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                    const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
                    int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
@@ -417,6 +449,7 @@ static int mr_loss(const char *who, const int *res, int n_res, const float *audi
     STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "%s: pop %d, n_targets %d", who, pop, n_targets);
     STITO_REQUIRE(n_slots >= 1, STITO_E_INVALID, "%s: %d target slots", who, n_slots);
     STITO_REQUIRE(pop % n_slots == 0, STITO_E_INVALID, "%s: population %d is not a multiple of the number of targets %d", who, pop, n_slots);
+    if (SD) STITO_TRY(mr_sd_channels(who, channels));
     STITO_REQUIRE(channels >= 1 && channels <= MR_MAX_CH && n_res * channels <= 64, STITO_E_INVALID, "Invalid number of channels: %d", channels);
     STITO_REQUIRE(norm_passes == 0 || norm_passes == 1, STITO_E_INVALID, "%s: norm_passes %d must be 0 or 1", who, norm_passes);
     STITO_REQUIRE(norm_passes == 0 || peaks_dev != nullptr, STITO_E_INVALID, "%s: norm_passes 1 needs the peaks", who);
@@ -433,9 +466,9 @@ static int mr_loss(const char *who, const int *res, int n_res, const float *audi
     const double *ysum = (const double *)(table_dev + p.mags_base + trows * p.row_floats);
     for (int i = 0; i < p.n_res; ++i) {
         const MrDev d = mr_dev(p, i, n_samples, (float *)table_dev, partial, 2);
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
-        hipLaunchKernelGGL(k_mrstft<false>, dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev, peaks_dev,
-                           norm_passes, channels, pop / n_slots, target_slot_dev, n_targets);
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false, SD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL((k_mrstft<false, SD>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev,
+                           peaks_dev, norm_passes, channels, pop / n_slots, target_slot_dev, n_targets);
         STITO_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_mrstft_final, dim3((unsigned)pop), dim3(64), 0, st, mr_sum(p), partial, ysum, channels, pop / n_slots,
@@ -447,8 +480,8 @@ static int mr_loss(const char *who, const int *res, int n_res, const float *audi
 extern "C" int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                                  const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
                                  void *workspace_dev, size_t workspace_bytes, void *stream) {
-    return mr_loss("stito_mrstft_loss", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets, pop,
-                   channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss<false>("stito_mrstft_loss", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets,
+                          pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int stito_mrstft_loss_slots(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
@@ -456,6 +489,24 @@ extern "C" int stito_mrstft_loss_slots(const int *res, int n_res, const float *a
                                        int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
                                        void *stream) {
     STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots: null target_slot_dev");
-    return mr_loss("stito_mrstft_loss_slots", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots,
-                   pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss<false>("stito_mrstft_loss_slots", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
+                          target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+}
+
+// The sum / difference variants (ABI 10.7): the same calls on the 2-channel signal [L + R, L - R] of every item, against a table
+// that stito_mrstft_target_sd wrote.
+extern "C" int stito_mrstft_loss_sd(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                                    const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
+                                    void *workspace_dev, size_t workspace_bytes, void *stream) {
+    return mr_loss<true>("stito_mrstft_loss_sd", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets,
+                         pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int stito_mrstft_loss_slots_sd(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                                          const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
+                                          int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
+                                          void *stream) {
+    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots_sd: null target_slot_dev");
+    return mr_loss<true>("stito_mrstft_loss_slots_sd", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
+                         target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }

@@ -128,6 +128,11 @@ SIGNATURES = {
                                   c_void_p, c_size_t, c_void_p]),
     "stito_mrstft_loss_slots": (c_int, [POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                         c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "stito_mrstft_target_sd": (c_int, [POINTER(c_int), c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "stito_mrstft_loss_sd": (c_int, [POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "stito_mrstft_loss_slots_sd": (c_int, [POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                           c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "stito_spectral_centroid_workspace_bytes": (c_size_t, [c_int, c_int, c_int64]),
     "stito_spectral_centroid": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

@@ -653,18 +653,21 @@ class MrstftEvaluator(_Evaluator):
     objective's (eval_span) and ONE span serves input and target alike: the same zero padding to 262144, the same crop, and
     under random_crop the same start.  evaluate(W, pairs=[...], x=buffer, y=buffer) scores the populations of a SUBSET of the
     pairs on ready-made buffers, the counterpart of PopulationEvaluator.evaluate(W, pairs=, x=) -- the ragged batch;
-    `rendered_candidates` counts what went through the render.  Launches are eager.
+    `rendered_candidates` counts what went through the render.  Launches are eager.  stereo="sum-diff": the distance of the
+    render's [L + R, L - R] to the target's (features.MrstftTarget's mode, every table is built in it); the chain must render 2
+    channels.
 
     There are two kinds of target table.  The STATIC table of an evaluate-time length holds ALL the targets, for spans that
     never move: built once and read through a slot list.  A REFILLED table holds the targets of one call, for spans that move:
     one per (length, number of targets), rebuilt whenever the spans it holds are not the ones asked for."""
 
     def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor,
-                 device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False):
+                 device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False, stereo: str = "lr"):
         from . import features as _features
 
         if x.dim() != 3 or target_audio.dim() != 3:
             raise ValueError("input and target audio must be (batch, chs, seq_len)")
+        _features._mrstft_stereo(stereo, 2)  # the name; the chain's channel count is checked below, once it is known
         if target_audio.shape[0] != x.shape[0] or target_audio.shape[-1] != x.shape[-1]:
             raise ValueError(f"target audio {tuple(target_audio.shape)} does not cover the input {tuple(x.shape)}: the MRSTFT "
                              "objective compares sample spans, so batch and length must be equal")
@@ -672,6 +675,9 @@ class MrstftEvaluator(_Evaluator):
         super().__init__(x, sample_rate, plugins, device, normalize_stages)
         self.resolutions = resolutions
         c_out = _hip.lib().stito_chain_out_channels(self.chain[0], len(plugins), x.shape[1])
+        if stereo == "sum-diff" and c_out != 2:
+            raise ValueError(f"the sum / difference distance needs 2 channels, the chain renders {c_out}")
+        self.stereo = stereo
         if target_audio.shape[1] != c_out:
             raise ValueError(f"target audio has {target_audio.shape[1]} channels, the chain renders {c_out}")
         self.y_full = target_audio.to(self.device, torch.float32).contiguous()
@@ -688,7 +694,7 @@ class MrstftEvaluator(_Evaluator):
         pairs = self._pairs(pairs, "targets", once=True)
         if y.dim() != 3 or y.shape[0] != len(pairs) or y.shape[-1] != int(length):
             raise ValueError(f"y must be ({len(pairs)}, chs, {int(length)}), got {tuple(y.shape)}")
-        self._static[int(length)] = (_features.MrstftTarget(y, self.resolutions), {b: k for k, b in enumerate(pairs)})
+        self._static[int(length)] = (_features.MrstftTarget(y, self.resolutions, self.stereo), {b: k for k, b in enumerate(pairs)})
 
     def _static_table(self, length: int):
         """-> (MrstftTarget, {pair: slot}) of ALL the targets at an evaluate-time length where no span moves: what
@@ -701,7 +707,7 @@ class MrstftEvaluator(_Evaluator):
             if not (length == n or n < length == CROP_LEN):
                 raise ValueError(f"no static targets of {length} samples (the evaluator's own have {n}): pass y")
             y, self._y_padded = cut_to_span(self.y_full, (0, length), self._y_padded)
-            ent = self._static[length] = (_features.MrstftTarget(y, self.resolutions), {b: b for b in range(self.n_inputs)})
+            ent = self._static[length] = (_features.MrstftTarget(y, self.resolutions, self.stereo), {b: b for b in range(self.n_inputs)})
         return ent
 
     def _input_and_target(self, random_crop: bool, rng, parallel: bool = False):
@@ -719,7 +725,7 @@ class MrstftEvaluator(_Evaluator):
         key = (y.shape[-1], y.shape[0])
         ent = self._refilled.get(key)
         if ent is None:
-            ent = self._refilled[key] = [_features.MrstftTarget(y, self.resolutions), held]
+            ent = self._refilled[key] = [_features.MrstftTarget(y, self.resolutions, self.stereo), held]
         elif held is None or ent[1] != held:
             ent[0].update(y)
             ent[1] = held

@@ -279,14 +279,26 @@ def _mrstft_check_length(n: int, resolutions) -> None:
         raise ValueError(f"{int(n)} samples are too few for the reflect padding of n_fft {2 * half} (more than {half} are needed)")
 
 
+def _mrstft_stereo(stereo, channels) -> bool:
+    """True for stereo="sum-diff", False for "lr"; ValueError for anything else and for sum / difference of other than 2 channels."""
+    if stereo not in ("lr", "sum-diff"):
+        raise ValueError(f"stereo must be 'lr' or 'sum-diff', got {stereo!r}")
+    if stereo == "sum-diff" and int(channels) != 2:
+        raise ValueError(f"the sum / difference distance needs 2 channels, got {int(channels)}")
+    return stereo == "sum-diff"
+
+
 class MrstftTarget:
     """The target side of the distance on the device: the table stito_mrstft_target writes for y (T, C, n) -- FFT tables,
-    clamped magnitudes per (row, resolution), sum |Y|^2 -- in a buffer that `update` refills for another y of the same shape."""
+    clamped magnitudes per (row, resolution), sum |Y|^2 -- in a buffer that `update` refills for another y of the same shape.
+    stereo="sum-diff": the rows of a target are its L + R and L - R (stito_mrstft_target_sd) and `loss` forms the same two rows of
+    every candidate in its loader -- auraloss's SumAndDifferenceSTFTLoss with both weights 1; 2-channel audio only."""
 
-    def __init__(self, y: torch.Tensor, resolutions=None):
+    def __init__(self, y: torch.Tensor, resolutions=None, stereo: str = "lr"):
         self.res, self.n_res = _mrstft_res(resolutions)
         if y.dim() != 3:
             raise ValueError("expected (n_targets, chs, seq_len)")
+        self.sum_diff = _mrstft_stereo(stereo, y.shape[1])
         _mrstft_check_length(y.shape[-1], resolutions)
         self.resolutions = resolutions
         self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
@@ -301,15 +313,21 @@ class MrstftTarget:
         if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
             raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
         y = y.contiguous()
-        _hip.check(_hip.lib().stito_mrstft_target(self.res, self.n_res, _hip.ptr(y), self.n_targets * self.channels, self.n,
-                                                  _hip.ptr(self.table), _hip.stream_ptr()))
+        L = _hip.lib()
+        if self.sum_diff:
+            _hip.check(L.stito_mrstft_target_sd(self.res, self.n_res, _hip.ptr(y), self.n_targets, self.channels, self.n,
+                                                _hip.ptr(self.table), _hip.stream_ptr()))
+        else:
+            _hip.check(L.stito_mrstft_target(self.res, self.n_res, _hip.ptr(y), self.n_targets * self.channels, self.n,
+                                             _hip.ptr(self.table), _hip.stream_ptr()))
         return self
 
     def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None) -> torch.Tensor:
         """audio (P, C, n) float32 on the GPU, P a multiple of the number of targets (candidate p against target p // (P // T))
         -> (P,) float32.  norm_passes 1: audio[p] / clip(peaks[p], 1e-8) is what gets scored, folded into the kernel's loader.
         slots: (K,) int32 on the GPU, P a multiple of K -- the K stacked populations are scored against the targets slots[k] of
-        the table (stito_mrstft_loss_slots: any subset, any order; a slot that names no target gives NaN)."""
+        the table (stito_mrstft_loss_slots: any subset, any order; a slot that names no target gives NaN).  A sum / difference
+        table goes through the _sd entry points, same arguments."""
         from .engine import _WS
 
         if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
@@ -320,16 +338,17 @@ class MrstftTarget:
         L = _hip.lib()
         ws = _WS.get("mrstft", L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device)
         out = torch.empty(P, dtype=torch.float32, device=audio.device)
+        plain, with_slots = ((L.stito_mrstft_loss_sd, L.stito_mrstft_loss_slots_sd) if self.sum_diff else
+                             (L.stito_mrstft_loss, L.stito_mrstft_loss_slots))
         if slots is None:
-            _hip.check(L.stito_mrstft_loss(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
-                                           self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(),
-                                           _hip.stream_ptr()))
+            _hip.check(plain(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+                             self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
             return out
         if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
             raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
-        _hip.check(L.stito_mrstft_loss_slots(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
-                                             self.n_targets, _hip.ptr(slots), slots.numel(), P, self.channels, self.n, _hip.ptr(out),
-                                             _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
+        _hip.check(with_slots(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+                              self.n_targets, _hip.ptr(slots), slots.numel(), P, self.channels, self.n, _hip.ptr(out),
+                              _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
         return out
 
 
@@ -338,12 +357,24 @@ def compute_mrstft_distance(x: torch.Tensor, y: torch.Tensor, resolutions=None) 
     the mean of these); x (B, C, n) the estimate, y (B, C, n) or (1, C, n) the reference.  resolutions: triples (n_fft, hop,
     win), default auraloss's (1024, 120, 600), (2048, 240, 1200), (512, 50, 240).  One fused kernel per resolution
     (stito_mrstft_loss): the spectra never reach HBM."""
+    return _mrstft_distance(x, y, resolutions, "lr")
+
+
+def compute_sd_mrstft_distance(x: torch.Tensor, y: torch.Tensor, resolutions=None) -> torch.Tensor:
+    """auraloss.freq.SumAndDifferenceSTFTLoss()(x[b], y[b]) per item with both weights 1 (restated, unpinned): the distance of
+    compute_mrstft_distance applied to [L + R, L - R] (no factor 1/2) of the estimate and of the reference.  Same shape rules;
+    x and y must have 2 channels.  The sums and differences are formed in the kernel's loader (stito_mrstft_loss_sd)."""
+    return _mrstft_distance(x, y, resolutions, "sum-diff")
+
+
+def _mrstft_distance(x, y, resolutions, stereo):
     if x.dim() != 3 or y.dim() != 3:
         raise ValueError("expected (bs, chs, seq_len)")
     if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
         raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _mrstft_stereo(stereo, x.shape[1])
     _mrstft_res(resolutions)
     _mrstft_check_length(x.shape[-1], resolutions)
     xin, dev = _gpu(x)
     yin = y.detach().to(dev, torch.float32).contiguous()
-    return MrstftTarget(yin, resolutions).loss(xin).to(x.device)
+    return MrstftTarget(yin, resolutions, stereo).loss(xin).to(x.device)

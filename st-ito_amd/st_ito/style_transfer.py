@@ -15,7 +15,7 @@ The three ES drivers share one statement of each rule: `_EsRun` is one CMA-ES tr
 `_peak_normalize_` and `_chain_dims` are the steps every driver takes before its first iteration.  `run_es` steps one `_EsRun`,
 `run_es_batch` a list of them, `run_staged_es` builds one per stage and keeps run_optim.py's own post-tell histories.  The
 objective (`distance`) is likewise said once for all three: `_check_distance`, `_check_mrstft_pairs` (what distance="mrstft"
-asks of a pair) and `_make_evaluator`, the one place that picks the engine's evaluator; the loops see losses only.
+and "mrstft-sd" ask of a pair) and `_make_evaluator`, the one place that picks the engine's evaluator; the loops see losses only.
 """
 from __future__ import annotations
 
@@ -416,13 +416,13 @@ def run_es(
     if content_model is not None and content_embed_func is None:
         raise ValueError("content_model needs a content_embed_func")
     bs, chs, seq_len = input_audio.shape
-    if distance == "mrstft":
-        _check_mrstft_pairs(input_audio, target_audio, plugins, "the target")
+    if distance in _AUDIO_DISTANCES:
+        _check_mrstft_pairs(input_audio, target_audio, plugins, "the target", distance=distance)
         if content_model is not None:
-            raise ValueError("distance 'mrstft' has no embeddings: content_model cannot be used with it")
+            raise ValueError(f"distance '{distance}' has no embeddings: content_model cannot be used with it")
         if dropout > 0:
-            raise ValueError("distance 'mrstft' has no embeddings: dropout must be 0")
-        _check_mrstft_savepop(savepop)
+            raise ValueError(f"distance '{distance}' has no embeddings: dropout must be 0")
+        _check_mrstft_savepop(savepop, distance)
     seed = _agree_on_seed(seed)
     rng = np.random.RandomState(seed) if seed is not None else np.random
 
@@ -433,7 +433,7 @@ def run_es(
     options = dict(max_iters=max_iters, w0=w0, find_w0=find_w0, sigma0=sigma0, random_crop=random_crop, popsize=popsize,
                    parallel=parallel, dropout=dropout, savepop=savepop, run_dir=run_dir, seed=seed, rng=rng, early_stop=early_stop,
                    device_es=device_es, sync_every=sync_every)
-    if distance == "mrstft":
+    if distance in _AUDIO_DISTANCES:
         # the objective is the distance to the target AUDIO: no model, no embedding, nothing to compute once but the target's
         # magnitude table, which the evaluator builds for the span it evaluates
         evaluator = _make_evaluator(distance, input_audio, sample_rate, plugins, None, target_audio)
@@ -486,38 +486,48 @@ def _check_device_es(plugins, popsize, max_iters, savepop, sync_every):
     cma.device_es_state_bytes(sum(plugin["num_params"] for plugin in plugins.values()), popsize, max_iters)
 
 
+# the objectives that compare the rendered AUDIO with the target's: "mrstft" channel by channel, "mrstft-sd" on [L + R, L - R]
+_AUDIO_DISTANCES = ("mrstft", "mrstft-sd")
+
+
 def _check_distance(distance):
-    if distance not in ("cosine", "mrstft"):
+    if distance != "cosine" and distance not in _AUDIO_DISTANCES:
         raise ValueError(f"Unknown distance: {distance}")
 
 
-def _check_mrstft_pairs(input_audios, target_audios, plugins, target="target {b}", chain="the chain"):
-    """The pair rule of distance="mrstft", said before anything is launched: the distance compares sample spans of the render
-    and of the target, so a target has its input's length and the chain's output channel count.  input_audios / target_audios:
-    lists of (chs, n), or the rows of (B, chs, n) tensors; target / chain: what the messages call the two sides."""
+def _check_mrstft_pairs(input_audios, target_audios, plugins, target="target {b}", chain="the chain", distance="mrstft"):
+    """The pair rule of the audio distances, said before anything is launched: they compare sample spans of the render and of
+    the target, so a target has its input's length and the chain's output channel count -- which is 2 under "mrstft-sd", the
+    distance of sums and differences of two channels.  input_audios / target_audios: lists of (chs, n), or the rows of (B, chs,
+    n) tensors; target / chain: what the messages call the two sides."""
     if len(target_audios) != len(input_audios):
-        raise ValueError(f"distance 'mrstft': {len(input_audios)} inputs but {len(target_audios)} targets")
+        raise ValueError(f"distance '{distance}': {len(input_audios)} inputs but {len(target_audios)} targets")
     for b, (x, t) in enumerate(zip(input_audios, target_audios)):
         who = target.format(b=b)
         if t.dim() != 2 or t.shape[-1] != x.shape[-1]:
-            raise ValueError(f"distance 'mrstft' compares sample spans: {who} {tuple(t.shape)} must have the length of its input "
+            raise ValueError(f"distance '{distance}' compares sample spans: {who} {tuple(t.shape)} must have the length of its input "
                              f"{tuple(x.shape)}")
         c_out = engine.chain_out_channels(plugins, x.shape[0])
+        if distance == "mrstft-sd" and c_out != 2:
+            raise ValueError(f"distance 'mrstft-sd' compares the sums and differences of 2 channels: {chain} renders {c_out} channels "
+                             f"from input {b}'s {x.shape[0]}")
         if t.shape[0] != c_out:
-            raise ValueError(f"distance 'mrstft': {who} has {t.shape[0]} channels, {chain} renders {c_out}")
+            raise ValueError(f"distance '{distance}': {who} has {t.shape[0]} channels, {chain} renders {c_out}")
 
 
-def _check_mrstft_savepop(savepop):
+def _check_mrstft_savepop(savepop, distance="mrstft"):
     if savepop:
-        raise ValueError("distance 'mrstft' does not write populations: savepop is not supported")
+        raise ValueError(f"distance '{distance}' does not write populations: savepop is not supported")
 
 
 def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
     """The one place that turns `distance` into an evaluator, both resolved through `engine` when called.  target: the target
-    embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft", which
-    embeds nothing and launches eagerly: kw has nothing to say to it)."""
+    embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft" and
+    "mrstft-sd", which embed nothing and launch eagerly: kw has nothing to say to them)."""
     if distance == "mrstft":
         return engine.MrstftEvaluator(x, sample_rate, plugins, target)
+    if distance == "mrstft-sd":
+        return engine.MrstftEvaluator(x, sample_rate, plugins, target, stereo="sum-diff")
     return engine.PopulationEvaluator(x, sample_rate, plugins, model, target, **kw)
 
 
@@ -665,15 +675,16 @@ def run_staged_es(
 
     distance="mrstft": every stage scores its sub-chain's render against the full target AUDIO with an engine.MrstftEvaluator
     (model and embed_func may be None, nothing is embedded); everything else is as above.  Every stage's sub-chain must
-    render the target's channel count, and savepop is refused as run_es refuses it for this objective."""
+    render the target's channel count, and savepop is refused as run_es refuses it for this objective.  distance="mrstft-sd"
+    is the same with the sum / difference distance: every stage's sub-chain must render 2 channels."""
     _check_distance(distance)
     savepop = bool(savepop or save_pop)
     names = list(plugins.keys())
-    if distance == "mrstft":  # every stage compares its sub-chain's render with the full target
+    if distance in _AUDIO_DISTANCES:  # every stage compares its sub-chain's render with the full target
         for stage_idx in range(len(names)):
             _check_mrstft_pairs(input_audio, target_audio, {k: plugins[k] for k in names[: stage_idx + 1]}, "the target",
-                                f"stage {stage_idx} ({names[stage_idx]})")
-        _check_mrstft_savepop(savepop)
+                                f"stage {stage_idx} ({names[stage_idx]})", distance=distance)
+        _check_mrstft_savepop(savepop, distance)
     _, rank, world = _dist_info()
     seed = _agree_on_seed(seed)
     _peak_normalize_(input_audio)
@@ -781,15 +792,18 @@ def run_es_batch(
     packed like the inputs (a second engine.RaggedInputs); a length group whose spans can move (random_crop with a member
     that draws its crops) cuts the active pairs' target crops at the same starts as their inputs, one more gather per
     iteration, and refills the target table from them; a group whose spans cannot move gathers its targets once, its table
-    is built once, and pairs that stop drop out of it through the slot list of stito_mrstft_loss_slots."""
+    is built once, and pairs that stop drop out of it through the slot list of stito_mrstft_loss_slots.
+
+    distance="mrstft-sd": the same on both forms and on every path of the list form, with the distance taken between the sums
+    and differences of the two channels (MrstftEvaluator(stereo="sum-diff")); the chain must render exactly 2 channels."""
     _check_distance(distance)
     ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
     if ragged:
         input_audios, target_audios = _check_ragged_pairs(input_audios, target_audios)
     elif input_audios.dim() != 3 or target_audios.dim() != 3 or input_audios.shape[0] != target_audios.shape[0]:
         raise ValueError("input_audios and target_audios must be (B, chs, seq_len) with the same B")
-    if distance == "mrstft":
-        _check_mrstft_pairs(input_audios, target_audios, plugins)
+    if distance in _AUDIO_DISTANCES:
+        _check_mrstft_pairs(input_audios, target_audios, plugins, distance=distance)
     dist, rank, world = _dist_info()
     seed = _agree_on_seed(seed)
     B_all = len(input_audios)
@@ -803,7 +817,7 @@ def run_es_batch(
             xs, ts = input_audios[lo:hi].clone(), target_audios[lo:hi].clone()
         for a in (*xs, *ts):  # every pair on its own (run_es 452-453); the rows of a tensor are views of the clone
             _peak_normalize_(a)
-        target = ts  # "mrstft": the audio itself
+        target = ts  # the audio distances: the audio itself
         if distance == "cosine":
             # target embeddings, once: targets of equal shape in one embed_func call
             by_shape, rows = {}, [None] * len(ts)
@@ -823,7 +837,7 @@ def run_es_batch(
 
         pair_seeds = [None if seed is None else seed + lo + b for b in range(hi - lo)]  # CMA-ES and, in the list form, crops
         if ragged:
-            evaluator, submit = _ragged_form(make_evaluator, xs, ts if distance == "mrstft" else None, random_crop,
+            evaluator, submit = _ragged_form(make_evaluator, xs, ts if distance in _AUDIO_DISTANCES else None, random_crop,
                                              [rng_of(s) for s in pair_seeds])
         else:
             evaluator, submit = _tensor_form(make_evaluator, xs, random_crop, rng_of(seed))
