@@ -24,7 +24,13 @@ Operands: %0 = z (in/out), %1 = (S0, S1), %2 = (S2, S3), %3 = 64-bit load addres
 The committed file (tests/test_generated_sources.py holds it to this output byte for byte; the instruction count per block goes
 to stderr):
 
-    python tools/gen/gen_comp_scan_asm.py > st-ito_amd/csrc/comp_scan.inc"""
+    python tools/gen/gen_comp_scan_asm.py > st-ito_amd/csrc/comp_scan.inc
+
+With the argument `stage` it prints st-ito_amd/csrc/comp_stage.inc instead: the same chain for the scan wave of k_comp_stage,
+which reads the block functions from LDS (ds_read_b128, a short register look-ahead) where helper waves of the same
+workgroup put them, and leaves the boundary states in LDS (tests/test_gpu_comp_stage.py holds that file to this output):
+
+    python tools/gen/gen_comp_scan_asm.py stage > st-ito_amd/csrc/comp_stage.inc"""
 import sys
 
 D = 32            # ring depth in blocks (compressor.hip: CB_D)
@@ -80,6 +86,125 @@ def prologue():
     L += [f"v_mov_b32 v{ZQ[0] + u}, 0" for u in range(4)]
     L += [f"global_store_dwordx4 %1, {quad(ZQ[0])}, off offset:{g * 16}" for g in range(D // 4)]
     return L
+
+# ---- mode "stage": the scan wave of k_comp_stage -- one segment of G blocks per asm statement, block functions out of LDS ----
+G = 64            # blocks per segment (compressor.hip: CS_G)
+DL = 8            # look-ahead in blocks: ds_read_b128 of block k + DL sits where the HBM ring's refill sat
+SBUF = 40         # v40 .. v40 + 4 DL - 1: look-ahead ring; every register lives inside the one statement (clobbers say it all)
+SZQ = [SBUF + 4 * DL, SBUF + 4 * DL + 4]
+ST = SZQ[1] + 4
+SNREG = ST + 6 - SBUF
+ZOFF = 16         # bytes: state after block i of the segment at float 4 + i of the stream's state row, the incoming state at float 3
+
+def stage_segment():
+    """Operands: %0 = z (in/out), %1 = (S0, S1), %2 = (S2, S3), %3 = LDS byte address of this lane's quad of block 0,
+    %4 = LDS byte address of the stream's state row.  LDS operations retire in issue order: `issued` counts them and
+    every wait is the number issued after the youngest one it needs."""
+    L, issued, idx = [], 0, {}
+    L.append("ds_write_b32 %4, %0 offset:12")
+    issued += 1
+    for k in range(DL):
+        L.append(f"ds_read_b128 {quad(SBUF + 4 * k)}, %3 offset:{k * 64}")
+        idx[k] = issued
+        issued += 1
+    zreg = None
+    for g in range(G // 4):
+        zq = SZQ[g & 1]
+        wait = issued - 1 - idx[4 * g + 3]
+        assert 0 <= wait <= 15
+        L.append(f"s_waitcnt lgkmcnt({wait})")
+        for u in range(4):
+            k = 4 * g + u
+            b = SBUF + 4 * (k % DL)
+            if zreg is None:
+                L.append(f"v_mov_b32 v{ST + 4}, %0")
+                zreg = ST + 4
+            zp, sel = zsrc(zreg)
+            L.append(f"v_pk_fma_f32 {pair(ST)}, %1, {zp}, {pair(b)} {sel}")
+            L.append(f"v_pk_fma_f32 {pair(ST + 2)}, %2, {zp}, {pair(b + 2)} {sel}")
+            L.append(f"v_max_f32 v{ST + 4}, v{ST}, v{ST + 1}")
+            L.append(f"v_max3_f32 v{ST + 4}, v{ST + 4}, v{ST + 2}, v{ST + 3}")
+            if k + DL < G:
+                L.append(f"ds_read_b128 {quad(b)}, %3 offset:{(k + DL) * 64}")
+                idx[k + DL] = issued
+                issued += 1
+                L.append("s_nop 0")
+            else:
+                L.append("s_nop 1")
+            L.append(f"v_max_f32_dpp v{ST + 5}, v{ST + 4}, v{ST + 4} quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+            if u == 3 and g > 0:
+                L.append(f"ds_write_b128 %4, {quad(SZQ[(g - 1) & 1])} offset:{ZOFF + (g - 1) * 16}")
+                issued += 1
+                L.append("s_nop 0")
+            else:
+                L.append("s_nop 1")
+            L.append(f"v_max_f32_dpp v{zq + u}, v{ST + 5}, v{ST + 5} quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+            zreg = zq + u
+    L.append(f"ds_write_b128 %4, {quad(SZQ[(G // 4 - 1) & 1])} offset:{ZOFF + (G // 4 - 1) * 16}")
+    L.append(f"v_mov_b32 %0, v{zreg}")
+    L.append("s_waitcnt lgkmcnt(0)")
+    return L
+
+K = 15            # samples per block (compressor.hip: CB_K)
+XBUF = 40         # v40 .. v40 + 2 K - 1: the samples of both chains, step n at v[40 + 2 n : 41 + 2 n]
+PP = XBUF + 2 * K  # two sets of (a, r) pairs for chain a and chain b: the set of step n + 1 is formed under step n
+PT = PP + 8       # two pairs (c_att B + a, c_rel B + r); B lives in the high half
+
+def stage_blockfn2():
+    """The helpers' block-function recurrence for TWO units (2 x 4 blocks, one per 16-lane row) at once: per step and chain two
+    v_mul_f32 ((a, r) = (sa |x|, sr |x|), off the chain), one v_pk_fma_f32 (lane j: c_att B_j + a for lane j + 1, c_rel B_j + r for
+    itself) and one v_max_f32_dpp row_shr:1 (lane 0 of a row has no source lane and keeps c_rel B_0 + r = max(-inf, .)).  The two
+    chains and the next step's products fill each other's hazard slots.  A row reads ONE float per step and chain from LDS (the
+    sample, broadcast): the pairs themselves, 16 bytes a lane, made the LDS the kernel's limit.
+    Operands: %0, %1 = B_0.. of chain a, b (out), %2 = (c_att, c_rel), %3 = sa, %4 = sr, %5 = B at the start (0 in lane 0 of a row, -inf
+    elsewhere), %6 = LDS byte address of chain a's samples of this lane's row; chain b's sit 4 K floats behind."""
+    L = [f"ds_read2_b32 {pair(XBUF + 2 * n)}, %6 offset0:{n} offset1:{4 * K + n}" for n in range(K)]
+    L.append(f"v_mov_b32 v{PT + 1}, %5")
+    L.append(f"v_mov_b32 v{PT + 3}, %5")
+    hi = "op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+    def muls(n, chain):
+        x, p = XBUF + 2 * n + chain, PP + 4 * (n & 1) + 2 * chain
+        return [f"v_mul_f32_e64 v{p}, %3, |v{x}|", f"v_mul_f32_e64 v{p + 1}, %4, |v{x}|"]
+    L.append(f"s_waitcnt lgkmcnt({K - 1})")
+    L += muls(0, 0) + muls(0, 1)
+    for n in range(K):
+        p = PP + 4 * (n & 1)
+        L.append(f"v_pk_fma_f32 {pair(PT)}, %2, {pair(PT)}, {pair(p)} {hi}")
+        L.append(f"v_pk_fma_f32 {pair(PT + 2)}, %2, {pair(PT + 2)}, {pair(p + 2)} {hi}")
+        if n + 1 < K:
+            L.append(f"s_waitcnt lgkmcnt({K - 2 - n})")
+            L += muls(n + 1, 0)
+        else:
+            L.append("s_nop 1")
+        L.append(f"v_max_f32_dpp v{PT + 1}, v{PT}, v{PT + 1} row_shr:1 row_mask:0xf bank_mask:0xf")
+        L.append(f"v_max_f32_dpp v{PT + 3}, v{PT + 2}, v{PT + 3} row_shr:1 row_mask:0xf bank_mask:0xf")
+        if n + 1 < K:
+            L += muls(n + 1, 1)
+    L.append(f"v_mov_b32 %0, v{PT + 1}")
+    L.append(f"v_mov_b32 %1, v{PT + 3}")
+    return L
+
+if sys.argv[1:] == ["stage"]:
+    sclob = ", ".join(f'"v{r}"' for r in range(SBUF, SBUF + SNREG))
+    f = sys.stdout
+    f.write("// GENERATED by tools/gen/gen_comp_scan_asm.py stage -- do not edit.  k_comp_stage's scan wave: one segment of\n")
+    f.write(f"// {G} block functions read from LDS {DL} blocks ahead (v{SBUF}-v{SBUF + 4 * DL - 1}), states written to LDS; no register outlives the statement.\n")
+    f.write(f"#define STITO_COMP_STAGE_G {G}\n")
+    f.write("#define STITO_COMP_STAGE_SEGMENT(z, s01, s23, fn_lds, z_lds) \\\n    asm volatile( \\\n")
+    body = stage_segment()
+    for l in body:
+        f.write(f'        "{l}\\n\\t" \\\n')
+    f.write(f'        : "+v"(z) : "v"(s01), "v"(s23), "v"(fn_lds), "v"(z_lds) : "memory", {sclob})\n')
+    print(len(body), "instructions per segment of", G, "blocks =", len(body) / G, "per block", file=sys.stderr)
+    pclob = ", ".join(f'"v{r}"' for r in range(XBUF, PT + 4))
+    f.write("// the helper waves' recurrence, two units of four blocks at a time\n")
+    f.write("#define STITO_COMP_STAGE_BLOCKFN2(b_a, b_b, c2, sa, sr, b_init, x_lds) \\\n    asm volatile( \\\n")
+    body = stage_blockfn2()
+    for l in body:
+        f.write(f'        "{l}\\n\\t" \\\n')
+    f.write(f'        : "=&v"(b_a), "=&v"(b_b) : "v"(c2), "v"(sa), "v"(sr), "v"(b_init), "v"(x_lds) : "memory", {pclob})\n')
+    print(len(body), "instructions per two units of the block functions", file=sys.stderr)
+    sys.exit(0)
 
 clob = ", ".join(f'"v{r}"' for r in range(BUF, BUF + NREG))
 f = sys.stdout
