@@ -111,7 +111,8 @@ int stito_version(void);
  * stito_render_population(_multi); kinds 0 - 7 keep their numbers, parameter counts and bits); 3 = stito_barkspectrum_mixed,
  * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan; 4 = stito_mrstft_table_floats, stito_mrstft_target,
  * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots; 6 = the device-resident CMA-ES, stito_cmaes_*;
- * 7 = stito_mrstft_target_sd, stito_mrstft_loss_sd, stito_mrstft_loss_slots_sd. */
+ * 7 = stito_mrstft_target_sd, stito_mrstft_loss_sd, stito_mrstft_loss_slots_sd; 8 = stito_mel_bank, stito_mrstft_table_floats_mel,
+ * stito_mrstft_target_mel, stito_mrstft_loss_mel, stito_mrstft_loss_slots_mel. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -573,6 +574,49 @@ int stito_mrstft_loss_slots_sd(const int *res, int n_res, const float *audio_dev
                                const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
                                int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
                                void *stream);
+
+/* The mel variants (ABI 10.8): auraloss.freq.MultiResolutionSTFTLoss(scale="mel", n_bins=, sample_rate=) (restated, PARITY UNPINNED).
+ * Framing, window and clamped magnitude |X| are those above; per resolution M = F |X| with a bank F of n_bins bands over the n_fft / 2
+ * + 1 bins, and sc = || M_y - M_x ||_F / || M_y ||_F, lm = mean | ln M_x - ln M_y | over frames x n_bins; an item's loss is the mean
+ * over resolutions of the mean over its channel rows (L/R) of sc + lm.  The bank is the caller's: every band is ONE run of consecutive
+ * bins, band m of resolution i covering bins [band_start[i n_bins + m], + band_len[i n_bins + m]) with weight j of the run at
+ * weights_dev[w_offset[i] + j * w_stride[i] + m] -- the interleaved layout of stito_frontend.mel_w_dev: the lanes of a wave, one band
+ * each, read consecutive floats per step; w_rows[i] rows (the longest run of the resolution, shorter runs zero padded) of w_stride[i]
+ * >= n_bins floats.  band_start / band_len are given twice: on the HOST, where every call checks them before it asks the device
+ * anything, and on the device, where the kernel reads them (it cuts a run to the bins and rows that exist, so tables that differ from
+ * the checked ones cannot make it read outside).  STITO_E_INVALID: n_bins outside [1, 256], n_res other than the call's, a band longer
+ * than the bins or than w_rows, a band that starts beyond the bins or runs past them, w_stride < n_bins, a null table.  A band of
+ * length 0 is accepted here and gives M = 0, hence NaN, as in auraloss: the Python layer refuses such a bank.  A sum of magnitudes is
+ * a chain of fmas in bin order, so with the identity bank (n_bins = n_fft / 2 + 1, band k = bin k, weight 1) every term is the
+ * linear kernels' float32 value.
+ * stito_mrstft_table_floats_mel: the floats of a table of `rows` rows, smaller than the linear one (frames x n_bins per row and
+ * resolution).  stito_mrstft_target_mel / _loss_mel / _loss_slots_mel: stito_mrstft_target / _loss / _loss_slots with the bank after
+ * n_res, every other argument and every promise as there: candidate p against target p / (pop / n_targets), norm_passes folds the
+ * peak into the loader, a slot that names no target gives NaN and disturbs nobody else, the same bits at every position of every
+ * batch and under every slot list, loss(y, table_mel(y)) exactly 0.  The workspace does not depend on the bank:
+ * stito_mrstft_workspace_bytes holds.  The same bank must be given to the table and to the loss; the table does not record it. */
+typedef struct stito_mel_bank {
+    int32_t n_bins;                 /* bands per resolution, 1 .. 256 */
+    int32_t n_res;                  /* resolutions the tables cover */
+    const int32_t *band_start;      /* HOST  [n_res][n_bins] */
+    const int32_t *band_len;        /* HOST  [n_res][n_bins] */
+    const int32_t *band_start_dev;  /* the same two tables on the device */
+    const int32_t *band_len_dev;
+    const float *weights_dev;       /* device; resolution i at w_offset[i] */
+    int64_t w_offset[8];
+    int32_t w_stride[8];
+    int32_t w_rows[8];
+} stito_mel_bank;
+int64_t stito_mrstft_table_floats_mel(const int *res, int n_res, int n_bins, int rows, int64_t n_samples);
+int stito_mrstft_target_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *y_dev, int rows, int64_t n_samples,
+                            float *table_dev, void *stream);
+int stito_mrstft_loss_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *audio_dev, const float *peaks_dev,
+                          int norm_passes, const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples,
+                          float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int stito_mrstft_loss_slots_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *audio_dev, const float *peaks_dev,
+                                int norm_passes, const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots,
+                                int pop, int channels, int64_t n_samples, float *loss_dev, void *workspace_dev,
+                                size_t workspace_bytes, void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

@@ -24,7 +24,18 @@
 // distance of the 2-channel signal [L + R, L - R], no factor 1/2: only the loader differs.  Row 2 item is the sum row and row
 // 2 item + 1 the difference row; the workgroup reads the span of BOTH channels of its item and stores xL r1 + xR r1, respectively
 // xL r1 - xR r1 (two products and one add, uncontracted).  Table, workspace and everything behind the span are those of C = 2.
+//
+// The mel variant (template MEL; auraloss's scale="mel", restated) sums the clamped magnitudes into bands before the two terms are
+// taken: M = F |X| with a bank F the caller hands in (stito_mel_bank), sc and lm over frames x n_bins.  Loader, frame loop and FFT
+// are unchanged.  Once a frame is transformed, lane l takes the bin pairs (k, N/2 - k), k = l, l + 64, ... <= N/4: the two
+// magnitudes of a pair read exactly the two points Z[k] and Z[N/2 - k] of the packed transform, so the lane writes them back over
+// those two points (no other lane reads them) and the wave's FFT buffer becomes the frame's magnitudes, still in digit-reversed
+// order, with NO extra LDS.  Then lane l owns the bands l, l + 64, ...: one banded dot product each, a chain of explicit fmas in
+// bin order over the interleaved weights (weight j of band m at w[j * stride + m]: the lanes read consecutive floats per step).
+// The table holds frames x n_bins mel magnitudes per (row, resolution) and sum M_y^2; sums, tile tree and final launch are shared.
 #include "common.h"
+
+#include <type_traits>
 
 namespace stito {
 
@@ -41,7 +52,7 @@ static constexpr int MR_MAX_CH = 8;  // the final sum gives one lane of a wave t
 struct MrPlan {
     int n_res;
     int nfft[MR_MAX_RES], hop[MR_MAX_RES], win[MR_MAX_RES], log2_n2[MR_MAX_RES], F[MR_MAX_RES];
-    int64_t T[MR_MAX_RES], tiles[MR_MAX_RES], bins[MR_MAX_RES];
+    int64_t T[MR_MAX_RES], tiles[MR_MAX_RES], bins[MR_MAX_RES];  // bins: the columns of a table row (mel: the bands)
     size_t lds[MR_MAX_RES];
     int64_t hdr_off[MR_MAX_RES], mag_off[MR_MAX_RES], tile_off[MR_MAX_RES];
     int64_t row_floats, mags_base, tiles_total;
@@ -53,7 +64,9 @@ static size_t mr_lds_bytes(int N, int hop, int F) {
            ((size_t)(F - 1) * hop + N) * 4;
 }
 
-static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p) {
+// n_bins: 0 for the linear table (a row of a frame is its n_fft / 2 + 1 bins), else the bands of the mel table.  The LDS, the
+// tiles and the workspace do not depend on it.
+static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p, int n_bins = 0) {
     STITO_REQUIRE(res != nullptr, STITO_E_INVALID, "mrstft: null resolutions");
     STITO_REQUIRE(n_res >= 1 && n_res <= MR_MAX_RES, STITO_E_INVALID, "mrstft: %d resolutions, 1 .. %d are supported", n_res, MR_MAX_RES);
     // gfx950's LDS per workgroup: the plan also sizes the table and the workspace, so it asks no device (mr_device_fits does)
@@ -72,7 +85,7 @@ static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p) {
         while ((1 << l2) < N / 2) ++l2;
         p.log2_n2[i] = l2;
         p.T[i] = 1 + n / hop;
-        p.bins[i] = N / 2 + 1;
+        p.bins[i] = n_bins > 0 ? n_bins : N / 2 + 1;
         // frames per tile: as many as 32 while two workgroups fit a CU's 160 KB of LDS, else what one workgroup can hold
         static const int cand_F[] = {32, 28, 24, 20, 16, 12, 8, 4, 2, 1};
         int F = 0;
@@ -117,6 +130,16 @@ struct MrDev {
     double *partial;      // [row][tiles_total][K] + this resolution's tile offset * K
     int64_t tiles_total;
 };
+
+// The mel kernels' argument: MrDev (whose `bins` is then n_bins, the columns of the table) and this resolution's bank.  The
+// linear kernels keep MrDev itself, so their argument layout and code are what they were.
+struct MrDevMel : MrDev {
+    int n_bins, w_stride, w_rows;   // weight j < w_rows of band m at w[j * w_stride + m]
+    const int32_t *band_start;      // [n_bins] first bin of the band
+    const int32_t *band_len;        // [n_bins] its number of consecutive bins
+    const float *w;
+};
+template <bool MEL> using MrDevOf = std::conditional_t<MEL, MrDevMel, MrDev>;
 
 __device__ __forceinline__ float2 mr_cmul(float2 a, float2 b) {  // explicit fmas: the file is built with -ffp-contract=off
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
@@ -184,6 +207,52 @@ __device__ __forceinline__ float mr_magnitude(const MrDev &d, const float2 *buf,
     return sqrtf(fmaxf(fmaf(re, re, im * im), 1e-8f));
 }
 
+// The mel variant's two steps on a transformed frame.  mr_mel_magnitudes: buf, as floats, becomes the frame's clamped magnitudes --
+// |X[k]|, k < N2, at float 2 mr_pos(k) and |X[N2]| at float 1 (the imaginary slot of point 0, which pairs with itself).  Every
+// magnitude is mr_magnitude's value: the linear kernels' float32 bits.
+__device__ __forceinline__ void mr_mel_magnitudes(const MrDev &d, float2 *buf, const float2 *tw_s, int lane) {
+    const int N2 = d.N2;
+    float *mg = (float *)buf;
+    for (int k = lane; k <= (N2 >> 1); k += 64) {
+        const float a = mr_magnitude(d, buf, tw_s, k), b = mr_magnitude(d, buf, tw_s, N2 - k);
+        const int pa = mr_pos(k, d.log2_n2), pb = mr_pos((N2 - k) & (N2 - 1), d.log2_n2);
+        mg[2 * pa] = a;  // both points of the pair have been read, and no other lane reads them
+        if (k == 0) mg[1] = b; else mg[2 * pb] = b;
+    }
+    MR_WAVE_SYNC()
+}
+
+// Band m of the frame whose magnitudes mr_mel_magnitudes left in buf: sum_j w[j] |X[start + j]|, fmas in bin order.  The run is
+// cut to the bins and to the weight rows that exist (the host refuses such a bank; the device tables are not trusted).
+__device__ __forceinline__ float mr_mel_band(const MrDevMel &d, const float2 *buf, int m) {
+    const float *mg = (const float *)buf;
+    const int N2 = d.N2;
+    const int s = d.band_start[m];
+    int len = d.band_len[m];
+    if (s < 0 || s > N2) len = 0;
+    if (len > N2 + 1 - s) len = N2 + 1 - s;
+    if (len > d.w_rows) len = d.w_rows;
+    const float *w = d.w + m;
+    float acc = 0.0f;
+    // Eight steps at a time, their loads issued together: with two workgroups on a CU nothing else hides the weights' way from L2.
+    // A step past the run repeats the run's last bin with weight 0, and fma(0, v, acc) is acc: the bits of the plain chain.
+    constexpr int U = 8;
+    for (int j0 = 0; j0 < len; j0 += U) {
+        float wv[U], mv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u, jc = j < len ? j : len - 1;
+            const int k = s + jc;
+            const float wl = w[(int64_t)jc * d.w_stride];
+            wv[u] = j < len ? wl : 0.0f;
+            mv[u] = (k == N2) ? mg[1] : mg[2 * mr_pos(k, d.log2_n2)];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc = fmaf(wv[u], mv[u], acc);
+    }
+    return acc;
+}
+
 // Table target of candidate `cand`: population k = cand / per_target reads target slots[k], or target k when there is no slot
 // list (the identity map: stito_mrstft_loss).  -1 for a slot that names no target of the table.
 __device__ __forceinline__ int mr_target_of(int64_t cand, int per_target, const int32_t *__restrict__ slots, int n_targets) {
@@ -197,8 +266,9 @@ __device__ __forceinline__ int mr_target_of(int64_t cand, int per_target, const 
 //         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).  A candidate whose slot names no target
 //         reads nothing from the table and writes no partial: k_mrstft_final gives it NaN.
 // SD:     C = 2 and audio = (items, 2, n) on both sides; row 2 item + 0 is the item's L + R, row 2 item + 1 its L - R.
-template <bool TARGET, bool SD>
-__global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__restrict__ audio, const float *__restrict__ peaks,
+// MEL:    the table's rows are frames x n_bins band sums of the magnitudes, and both terms are taken between those.
+template <bool TARGET, bool SD, bool MEL>
+__global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDevOf<MEL> d, const float *__restrict__ audio, const float *__restrict__ peaks,
                                                       int norm_passes, int C, int per_target, const int32_t *__restrict__ slots,
                                                       int n_targets) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -250,8 +320,10 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDev d, const float *__r
     for (int f = wave; f < nf; f += MR_WAVES) {
         mr_frame_fft(d, span + f * d.hop, win_s, tw_s, buf, lane);
         float *mrow = mags + (t0 + f) * d.bins;
-        for (int k = lane; k <= N2; k += 64) {
-            const float mx = mr_magnitude(d, buf, tw_s, k);
+        if constexpr (MEL) mr_mel_magnitudes(d, buf, tw_s, lane);
+        for (int k = lane; k <= (MEL ? (int)d.bins - 1 : N2); k += 64) {  // k: a bin, or a band of the mel table
+            float mx;
+            if constexpr (MEL) mx = mr_mel_band(d, buf, k); else mx = mr_magnitude(d, buf, tw_s, k);
             if (TARGET) {
                 mrow[k] = mx;
                 acc0 += (double)(mx * mx);
@@ -361,6 +433,48 @@ static MrDev mr_dev(const MrPlan &p, int i, int64_t n, float *table, double *par
     return d;
 }
 
+// The bank as the calls take it, checked on the host tables before a device is asked anything.
+static int mr_bank_check(const char *who, const stito_mel_bank *b, const int *res, int n_res) {
+    STITO_REQUIRE(b != nullptr, STITO_E_INVALID, "%s: null bank", who);
+    STITO_REQUIRE(b->n_bins >= 1 && b->n_bins <= 256, STITO_E_INVALID, "%s: n_bins %d, 1 .. 256 are supported", who, b->n_bins);
+    STITO_REQUIRE(res != nullptr && n_res >= 1 && n_res <= MR_MAX_RES, STITO_E_INVALID, "%s: %d resolutions, 1 .. %d are supported", who, n_res, MR_MAX_RES);
+    STITO_REQUIRE(b->n_res == n_res, STITO_E_INVALID, "%s: the bank covers %d resolutions, the call has %d", who, b->n_res, n_res);
+    STITO_REQUIRE(b->band_start != nullptr && b->band_len != nullptr && b->band_start_dev != nullptr && b->band_len_dev != nullptr &&
+                      b->weights_dev != nullptr, STITO_E_INVALID, "%s: null bank table", who);
+    for (int i = 0; i < n_res; ++i) {
+        const int bins = res[3 * i] / 2 + 1;
+        STITO_REQUIRE(b->w_offset[i] >= 0 && b->w_rows[i] >= 1 && b->w_stride[i] >= b->n_bins, STITO_E_INVALID,
+                      "%s: weights of resolution %d: offset %lld, %d rows of %d floats for %d bands", who, i, (long long)b->w_offset[i],
+                      b->w_rows[i], b->w_stride[i], b->n_bins);
+        for (int m = 0; m < b->n_bins; ++m) {
+            const int s = b->band_start[i * b->n_bins + m], len = b->band_len[i * b->n_bins + m];
+            STITO_REQUIRE(len >= 0 && len <= bins && len <= b->w_rows[i], STITO_E_INVALID,
+                          "%s: band %d of resolution %d (n_fft %d) is %d bins long: there are %d bins and %d weight rows", who, m, i, res[3 * i],
+                          len, bins, b->w_rows[i]);
+            STITO_REQUIRE(s >= 0 && s <= bins - len, STITO_E_INVALID, "%s: band %d of resolution %d (n_fft %d) starts at bin %d with %d bins: there are %d",
+                          who, m, i, res[3 * i], s, len, bins);
+        }
+    }
+    return STITO_OK;
+}
+
+static MrDevMel mr_dev_mel(const MrDev &lin, const stito_mel_bank *b, int i) {
+    MrDevMel d;
+    static_cast<MrDev &>(d) = lin;
+    d.n_bins = b->n_bins; d.w_stride = b->w_stride[i]; d.w_rows = b->w_rows[i];
+    d.band_start = b->band_start_dev + (int64_t)i * b->n_bins;
+    d.band_len = b->band_len_dev + (int64_t)i * b->n_bins;
+    d.w = b->weights_dev + b->w_offset[i];
+    return d;
+}
+
+// The kernel's argument of resolution i: MrDev, or with the bank's tables behind it.
+template <bool MEL>
+static MrDevOf<MEL> mr_dev_of(const MrPlan &p, int i, int64_t n, float *table, double *partial, int K, const stito_mel_bank *bank) {
+    const MrDev d = mr_dev(p, i, n, table, partial, K);
+    if constexpr (MEL) return mr_dev_mel(d, bank, i); else return d;
+}
+
 static MrSum mr_sum(const MrPlan &p) {
     MrSum s;
     s.n_res = p.n_res; s.tiles_total = p.tiles_total;
@@ -396,12 +510,13 @@ static int mr_sd_channels(const char *who, int channels) {
 }
 
 // The one launch path of the table.  SD: y_dev is (rows / 2, 2, n) and row 2 t + 0 / 1 of the table is target t's L + R / L - R.
-template <bool SD>
+// MEL: the rows of the table are band sums through `bank`, which has been checked.
+template <bool SD, bool MEL = false>
 static int mr_target(const char *who, const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
-                     void *stream) {
+                     void *stream, const stito_mel_bank *bank = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
-    STITO_TRY(mr_plan(res, n_res, n_samples, p));
+    STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0));
     STITO_TRY(mr_device_fits(p));
     STITO_REQUIRE(rows >= 1, STITO_E_INVALID, "%s: %d rows", who, rows);
     STITO_REQUIRE(y_dev != nullptr && table_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);
@@ -410,11 +525,11 @@ static int mr_target(const char *who, const int *res, int n_res, const float *y_
     double *partial = sums + (int64_t)rows * p.n_res;
     for (int i = 0; i < p.n_res; ++i) {
         STITO_REQUIRE((int64_t)rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "%s: too many tiles", who);
-        const MrDev d = mr_dev(p, i, n_samples, table_dev, partial, 1);
+        const MrDevOf<MEL> d = mr_dev_of<MEL>(p, i, n_samples, table_dev, partial, 1, bank);
         hipLaunchKernelGGL(k_mrstft_tables, dim3((d.N + 255) / 256), dim3(256), 0, st, (float2 *)d.tw, (float *)d.win, d.N, p.win[i]);
         STITO_LAUNCH_CHECK();
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true, SD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
-        hipLaunchKernelGGL((k_mrstft<true, SD>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true, SD, MEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL((k_mrstft<true, SD, MEL>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
                            (const float *)nullptr, 0, 1, 1, (const int32_t *)nullptr, rows);
         STITO_LAUNCH_CHECK();
     }
@@ -438,13 +553,14 @@ extern "C" int stito_mrstft_target_sd(const int *res, int n_res, const float *y_
 
 // The one launch path of the loss: populations of pop / n_slots candidates, population k against target target_slot[k] of the
 // table's n_targets, or against target k when there is no slot list (then n_slots == n_targets).
-template <bool SD>
+template <bool SD, bool MEL = false>
 static int mr_loss(const char *who, const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                    const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
-                   int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+                   int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
+                   const stito_mel_bank *bank = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
-    STITO_TRY(mr_plan(res, n_res, n_samples, p));
+    STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0));
     STITO_TRY(mr_device_fits(p));
     STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "%s: pop %d, n_targets %d", who, pop, n_targets);
     STITO_REQUIRE(n_slots >= 1, STITO_E_INVALID, "%s: %d target slots", who, n_slots);
@@ -465,9 +581,9 @@ static int mr_loss(const char *who, const int *res, int n_res, const float *audi
     double *partial = (double *)workspace_dev;
     const double *ysum = (const double *)(table_dev + p.mags_base + trows * p.row_floats);
     for (int i = 0; i < p.n_res; ++i) {
-        const MrDev d = mr_dev(p, i, n_samples, (float *)table_dev, partial, 2);
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false, SD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
-        hipLaunchKernelGGL((k_mrstft<false, SD>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev,
+        const MrDevOf<MEL> d = mr_dev_of<MEL>(p, i, n_samples, (float *)table_dev, partial, 2, bank);
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false, SD, MEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL((k_mrstft<false, SD, MEL>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev,
                            peaks_dev, norm_passes, channels, pop / n_slots, target_slot_dev, n_targets);
         STITO_LAUNCH_CHECK();
     }
@@ -509,4 +625,35 @@ extern "C" int stito_mrstft_loss_slots_sd(const int *res, int n_res, const float
     STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots_sd: null target_slot_dev");
     return mr_loss<true>("stito_mrstft_loss_slots_sd", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
                          target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+}
+
+// The mel variants (ABI 10.8): the L/R calls with band sums M = F |X| in the place of the magnitudes, F the caller's bank.
+extern "C" int64_t stito_mrstft_table_floats_mel(const int *res, int n_res, int n_bins, int rows, int64_t n_samples) {
+    MrPlan p;
+    if (rows < 1 || n_bins < 1 || n_bins > 256 || mr_plan(res, n_res, n_samples, p, n_bins) != STITO_OK) return 0;
+    return mr_table_floats(p, rows);
+}
+
+extern "C" int stito_mrstft_target_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *y_dev, int rows,
+                                       int64_t n_samples, float *table_dev, void *stream) {
+    STITO_TRY(mr_bank_check("stito_mrstft_target_mel", bank, res, n_res));
+    return mr_target<false, true>("stito_mrstft_target_mel", res, n_res, y_dev, rows, n_samples, table_dev, stream, bank);
+}
+
+extern "C" int stito_mrstft_loss_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *audio_dev, const float *peaks_dev,
+                                     int norm_passes, const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples,
+                                     float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    STITO_TRY(mr_bank_check("stito_mrstft_loss_mel", bank, res, n_res));
+    return mr_loss<false, true>("stito_mrstft_loss_mel", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr,
+                                n_targets, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank);
+}
+
+extern "C" int stito_mrstft_loss_slots_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *audio_dev,
+                                           const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
+                                           const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples,
+                                           float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    STITO_TRY(mr_bank_check("stito_mrstft_loss_slots_mel", bank, res, n_res));
+    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots_mel: null target_slot_dev");
+    return mr_loss<false, true>("stito_mrstft_loss_slots_mel", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
+                                target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank);
 }

@@ -26,6 +26,9 @@ from st_ito.style_transfer import process_audio, run_es, run_staged_es  # noqa: 
 from st_ito.utils import get_param_embeds, load_param_model, make_synthetic_param_model  # noqa: E402
 
 
+AUDIO_OBJECTIVES = ("mrstft", "mrstft-sd", "mrstft-mel")  # --objective values that are run_es's `distance` as they stand
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("input", type=str)
@@ -51,10 +54,12 @@ def build_parser():
     parser.add_argument("--no-early-stop", action="store_true")
     parser.add_argument("--no-find-w0", action="store_true")
     parser.add_argument("--output-dir", type=str, default="output/optim")
-    parser.add_argument("--objective", type=str, default="embedding", choices=["embedding", "mrstft", "mrstft-sd"],
+    parser.add_argument("--objective", type=str, default="embedding", choices=["embedding", "mrstft", "mrstft-sd", "mrstft-mel"],
                         help="embedding: cosine distance of the --metric embeddings (the reference); mrstft: multi-resolution STFT "
                              "distance to the target audio itself (same length as the input; no checkpoint is loaded); mrstft-sd: "
-                             "that distance between the sums and differences of the two channels (a chain that renders stereo)")
+                             "that distance between the sums and differences of the two channels (a chain that renders stereo); mrstft-mel: "
+                             "that distance between 64 mel-band sums of the magnitudes, so the near-silent bins above a few kHz no "
+                             "longer carry it")
     parser.add_argument("--device-es", action="store_true",
                         help="step the CMA-ES on the GPU (run_es(device_es=True)): same update rule, its own random stream; single "
                              "rank, no --savepop, not with --staged")
@@ -116,7 +121,7 @@ def main(argv=None):
     run_dir = os.path.join(args.output_dir, run_name)
     os.makedirs(run_dir, exist_ok=True)
 
-    if args.objective in ("mrstft", "mrstft-sd"):
+    if args.objective in AUDIO_OBJECTIVES:
         model, embed_func = None, None  # the distance is taken on the audio: no checkpoint
     else:
         model = make_synthetic_param_model(seed=0) if args.synthetic else load_param_model(ckpt_path=args.ckpt, use_gpu=args.use_gpu)
@@ -134,7 +139,7 @@ def main(argv=None):
     result = es_func(
         input_audio.unsqueeze(0), target_audio.unsqueeze(0), sample_rate, plugins, model, embed_func,
         max_iters=args.max_iters, popsize=args.popsize, w0=w0, find_w0=not args.no_find_w0, sigma0=sigma0,
-        distance=args.objective if args.objective in ("mrstft", "mrstft-sd") else "cosine", parallel=args.parallel, dropout=args.dropout, savepop=args.savepop,
+        distance=args.objective if args.objective in AUDIO_OBJECTIVES else "cosine", parallel=args.parallel, dropout=args.dropout, savepop=args.savepop,
         normalize_stages=args.normalize_stages, run_dir=run_dir, seed=args.seed,
         early_stop=not args.no_early_stop,
         **({"device_es": True, "sync_every": args.sync_every} if args.device_es else {}),   # absent: the call as it always was

@@ -58,6 +58,16 @@ class Cnn14Weights(Structure):
     ]
 
 
+class MelBank(Structure):
+    """stito_mel_bank: band_start / band_len on the host (checked by every call) and on the device (read by the kernel)."""
+    _fields_ = [
+        ("n_bins", c_int32), ("n_res", c_int32),
+        ("band_start", POINTER(c_int32)), ("band_len", POINTER(c_int32)),
+        ("band_start_dev", c_void_p), ("band_len_dev", c_void_p), ("weights_dev", c_void_p),
+        ("w_offset", c_int64 * 8), ("w_stride", c_int32 * 8), ("w_rows", c_int32 * 8),
+    ]
+
+
 class StitoError(RuntimeError):
     pass
 
@@ -133,6 +143,13 @@ SIGNATURES = {
                                      c_void_p, c_size_t, c_void_p]),
     "stito_mrstft_loss_slots_sd": (c_int, [POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                            c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the mel variants (ABI 10.8): the L/R calls with the bank after n_res; the workspace is stito_mrstft_workspace_bytes'
+    "stito_mrstft_table_floats_mel": (c_int64, [POINTER(c_int), c_int, c_int, c_int, c_int64]),
+    "stito_mrstft_target_mel": (c_int, [POINTER(c_int), c_int, POINTER(MelBank), c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "stito_mrstft_loss_mel": (c_int, [POINTER(c_int), c_int, POINTER(MelBank), c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                      c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "stito_mrstft_loss_slots_mel": (c_int, [POINTER(c_int), c_int, POINTER(MelBank), c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                            c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "stito_spectral_centroid_workspace_bytes": (c_size_t, [c_int, c_int, c_int64]),
     "stito_spectral_centroid": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

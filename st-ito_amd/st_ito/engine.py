@@ -685,29 +685,32 @@ class MrstftEvaluator(_Evaluator):
         self._static = {}    # evaluate-time length -> (MrstftTarget of all targets, {pair: slot})
         self._refilled = {}  # (evaluate-time length, number of targets) -> [MrstftTarget, the spans it holds (None: a caller's y)]
 
+    def _target_table(self, y: torch.Tensor):
+        """The one place a target table is made, for y (targets, C', length) on the device: the kind of distance is the kind of
+        table (MelMrstftEvaluator overrides this)."""
+        from . import features as _features
+
+        return _features.MrstftTarget(y, self.resolutions, self.stereo)
+
     def set_static_targets(self, length: int, pairs, y: torch.Tensor) -> None:
         """The static table of one evaluate-time length, for an evaluator whose own audio is a stand-in (the ragged batch): y
         (len(pairs), C', length) float32 on the device holds the target spans of the listed pairs, which never move.  Built
         once; evaluate(W, pairs=, x=) without y then scores any subset of these pairs through the slot list."""
-        from . import features as _features
-
         pairs = self._pairs(pairs, "targets", once=True)
         if y.dim() != 3 or y.shape[0] != len(pairs) or y.shape[-1] != int(length):
             raise ValueError(f"y must be ({len(pairs)}, chs, {int(length)}), got {tuple(y.shape)}")
-        self._static[int(length)] = (_features.MrstftTarget(y, self.resolutions, self.stereo), {b: k for k, b in enumerate(pairs)})
+        self._static[int(length)] = (self._target_table(y), {b: k for k, b in enumerate(pairs)})
 
     def _static_table(self, length: int):
         """-> (MrstftTarget, {pair: slot}) of ALL the targets at an evaluate-time length where no span moves: what
         set_static_targets registered, else the evaluator's own targets as they are or zero padded to 262144 (built once)."""
-        from . import features as _features
-
         ent = self._static.get(length)
         if ent is None:
             n = self.y_full.shape[-1]
             if not (length == n or n < length == CROP_LEN):
                 raise ValueError(f"no static targets of {length} samples (the evaluator's own have {n}): pass y")
             y, self._y_padded = cut_to_span(self.y_full, (0, length), self._y_padded)
-            ent = self._static[length] = (_features.MrstftTarget(y, self.resolutions, self.stereo), {b: b for b in range(self.n_inputs)})
+            ent = self._static[length] = (self._target_table(y), {b: b for b in range(self.n_inputs)})
         return ent
 
     def _input_and_target(self, random_crop: bool, rng, parallel: bool = False):
@@ -720,12 +723,10 @@ class MrstftEvaluator(_Evaluator):
     def _refilled_table(self, y: torch.Tensor, held):
         """-> the MrstftTarget of y's shape holding y.  held: what names y's spans from call to call (a table that already holds
         them is not refilled), or None for a caller's buffer, which always refills."""
-        from . import features as _features
-
         key = (y.shape[-1], y.shape[0])
         ent = self._refilled.get(key)
         if ent is None:
-            ent = self._refilled[key] = [_features.MrstftTarget(y, self.resolutions, self.stereo), held]
+            ent = self._refilled[key] = [self._target_table(y), held]
         elif held is None or ent[1] != held:
             ent[0].update(y)
             ent[1] = held
@@ -776,3 +777,24 @@ class MrstftEvaluator(_Evaluator):
         self.rendered_candidates += Wn.shape[0]
         loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots)
         return loss, {}, (normalize_audio_(audio, peaks) if want_audio else None)
+
+
+class MelMrstftEvaluator(MrstftEvaluator):
+    """MrstftEvaluator with the mel-scaled distance (features.MelMrstftTarget; auraloss's scale="mel"): every table holds band sums
+    of the target's magnitudes through the Slaney bank of the evaluator's sample rate with n_bins bands, channels compared L/R.
+    The bank is built and checked on the host once, before the base class touches the device: a bank with an empty band is a
+    ValueError naming the band, the resolution and the sample rate.  Everything else -- the length policy, static and refilled
+    tables, the slot list, the folded peak -- is the base class's."""
+
+    def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor,
+                 device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False, n_bins: int = 64):
+        from . import features as _features
+
+        self._bank = _features.mel_mrstft_bank(sample_rate, n_bins, resolutions)
+        self.n_bins = int(n_bins)
+        super().__init__(x, sample_rate, plugins, target_audio, device, resolutions, normalize_stages)
+
+    def _target_table(self, y: torch.Tensor):
+        from . import features as _features
+
+        return _features.MelMrstftTarget(y, resolutions=self.resolutions, bank=self._bank)

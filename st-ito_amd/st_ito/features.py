@@ -302,17 +302,18 @@ class MrstftTarget:
         _mrstft_check_length(y.shape[-1], resolutions)
         self.resolutions = resolutions
         self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
-        floats = _hip.lib().stito_mrstft_table_floats(self.res, self.n_res, self.n_targets * self.channels, self.n)
+        floats = self._table_floats()
         if floats <= 0:
             raise ValueError(f"no MRSTFT table for {tuple(y.shape)} audio")
         self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
         self.update(y)
 
-    def update(self, y: torch.Tensor) -> "MrstftTarget":
-        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
-        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
-            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
-        y = y.contiguous()
+    # The three places where the kinds of table differ (MelMrstftTarget overrides them): the table's size, the call that fills
+    # it, and the two loss entry points with what they take between n_res and the audio.
+    def _table_floats(self) -> int:
+        return _hip.lib().stito_mrstft_table_floats(self.res, self.n_res, self.n_targets * self.channels, self.n)
+
+    def _fill(self, y: torch.Tensor) -> None:
         L = _hip.lib()
         if self.sum_diff:
             _hip.check(L.stito_mrstft_target_sd(self.res, self.n_res, _hip.ptr(y), self.n_targets, self.channels, self.n,
@@ -320,6 +321,19 @@ class MrstftTarget:
         else:
             _hip.check(L.stito_mrstft_target(self.res, self.n_res, _hip.ptr(y), self.n_targets * self.channels, self.n,
                                              _hip.ptr(self.table), _hip.stream_ptr()))
+
+    def _loss_calls(self):
+        """-> (the plain call, the call with a slot list, the arguments both take between n_res and audio_dev)"""
+        L = _hip.lib()
+        if self.sum_diff:
+            return L.stito_mrstft_loss_sd, L.stito_mrstft_loss_slots_sd, ()
+        return L.stito_mrstft_loss, L.stito_mrstft_loss_slots, ()
+
+    def update(self, y: torch.Tensor) -> "MrstftTarget":
+        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
+        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
+            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
+        self._fill(y.contiguous())
         return self
 
     def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None) -> torch.Tensor:
@@ -338,15 +352,14 @@ class MrstftTarget:
         L = _hip.lib()
         ws = _WS.get("mrstft", L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device)
         out = torch.empty(P, dtype=torch.float32, device=audio.device)
-        plain, with_slots = ((L.stito_mrstft_loss_sd, L.stito_mrstft_loss_slots_sd) if self.sum_diff else
-                             (L.stito_mrstft_loss, L.stito_mrstft_loss_slots))
+        plain, with_slots, between = self._loss_calls()
         if slots is None:
-            _hip.check(plain(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+            _hip.check(plain(self.res, self.n_res, *between, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
                              self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
             return out
         if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
             raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
-        _hip.check(with_slots(self.res, self.n_res, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
+        _hip.check(with_slots(self.res, self.n_res, *between, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
                               self.n_targets, _hip.ptr(slots), slots.numel(), P, self.channels, self.n, _hip.ptr(out),
                               _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
         return out
@@ -378,3 +391,121 @@ def _mrstft_distance(x, y, resolutions, stereo):
     xin, dev = _gpu(x)
     yin = y.detach().to(dev, torch.float32).contiguous()
     return MrstftTarget(yin, resolutions, stereo).loss(xin).to(x.device)
+
+
+# --------------------------------------------------------------------------------------------
+# its mel-scaled form (csrc/mrstft.hip's MEL variant)
+# --------------------------------------------------------------------------------------------
+MEL_MRSTFT_BINS = 64
+
+
+def mel_mrstft_bank(sample_rate, n_bins: int = MEL_MRSTFT_BINS, resolutions=None):
+    """The banks of auraloss's scale="mel" for a set of resolutions, built and checked on the host (no GPU needed): per
+    resolution librosa.filters.mel(sr=sample_rate, n_fft=n_fft, n_mels=n_bins) -- Slaney scale and norm, fmin 0, fmax sr / 2:
+    models.panns._mel_filterbank -- as (start (n_bins,) int32, length (n_bins,) int32, weights (longest run, n_bins) float32):
+    band m is the run of bins [start[m], start[m] + length[m]) from its first to its last non-zero weight, weight j of the run
+    at weights[j, m] (the interleaved layout of _hip.mel_tables).  ValueError for n_bins outside [1, 256] and for a band with no
+    non-zero weight (ln 0 on both sides: NaN in auraloss), naming the band, the resolution and the sample rate."""
+    from .models.panns import _mel_filterbank
+
+    _mrstft_res(resolutions)
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 256:
+        raise ValueError(f"n_bins {n_bins} must be in [1, 256]")
+    if not float(sample_rate) > 0:
+        raise ValueError(f"sample_rate {sample_rate} must be positive")
+    banks = []
+    for n_fft, hop, win in (MRSTFT_RESOLUTIONS if resolutions is None else resolutions):
+        n_fft = int(n_fft)
+        F = _mel_filterbank(float(sample_rate), n_fft, n_bins, 0.0, float(sample_rate) / 2)   # (n_bins, n_fft / 2 + 1) float32
+        start, length = np.zeros(n_bins, np.int32), np.zeros(n_bins, np.int32)
+        for m in range(n_bins):
+            nz = np.nonzero(F[m])[0]
+            if len(nz) == 0:
+                empty = [k for k in range(n_bins) if not F[k].any()]
+                raise ValueError(f"mel band {m} of {n_bins} has no non-zero weight at resolution ({n_fft}, {int(hop)}, {int(win)}) and "
+                                 f"sample rate {sample_rate} ({len(empty)} empty bands: {empty}): its ln 0 would be NaN; use fewer bands")
+            start[m], length[m] = nz[0], nz[-1] + 1 - nz[0]
+        weights = np.zeros((int(length.max()), n_bins), np.float32)
+        for m in range(n_bins):
+            weights[: length[m], m] = F[m, start[m]: start[m] + length[m]]
+        banks.append((start, length, weights))
+    return banks
+
+
+class _DeviceMelBank:
+    """A host bank (the triples of mel_mrstft_bank, or a test's) as the stito_mel_bank the calls take, with its device tables."""
+
+    def __init__(self, banks, device):
+        import ctypes
+
+        n_bins = len(banks[0][0])
+        self.start = np.ascontiguousarray(np.stack([np.asarray(b[0], np.int32) for b in banks]))
+        self.length = np.ascontiguousarray(np.stack([np.asarray(b[1], np.int32) for b in banks]))
+        weights = [np.ascontiguousarray(b[2], dtype=np.float32) for b in banks]
+        assert self.start.shape == self.length.shape == (len(banks), n_bins) and all(w.ndim == 2 for w in weights)
+        self.start_dev = torch.from_numpy(self.start).to(device)
+        self.length_dev = torch.from_numpy(self.length).to(device)
+        self.weights_dev = torch.from_numpy(np.concatenate([w.reshape(-1) for w in weights])).to(device)
+        c = self.c = _hip.MelBank()
+        c.n_bins, c.n_res = n_bins, len(banks)
+        c.band_start = self.start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        c.band_len = self.length.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        c.band_start_dev, c.band_len_dev = self.start_dev.data_ptr(), self.length_dev.data_ptr()
+        c.weights_dev = self.weights_dev.data_ptr()
+        off = 0
+        for i, w in enumerate(weights):
+            c.w_offset[i], c.w_stride[i], c.w_rows[i] = off, w.shape[1], w.shape[0]
+            off += w.size
+        self.ref = ctypes.byref(c)
+
+
+class MelMrstftTarget(MrstftTarget):
+    """MrstftTarget for the mel-scaled distance (auraloss.freq.MultiResolutionSTFTLoss(scale="mel", n_bins=, sample_rate=),
+    restated, unpinned): the table holds frames x n_bins band sums M = F |Y| per (row, resolution) and `loss` takes both terms
+    between band sums, the candidates' formed in the kernel from magnitudes that stay in LDS.  Channels are compared L/R.  The
+    bank is mel_mrstft_bank's (refused there, before anything is launched, when a band is empty), or `bank`: a list of
+    (start, length, weights) per resolution in that layout."""
+
+    def __init__(self, y: torch.Tensor, sample_rate=None, n_bins: int = MEL_MRSTFT_BINS, resolutions=None, bank=None):
+        if bank is None:
+            if sample_rate is None:
+                raise ValueError("MelMrstftTarget needs a sample_rate (or a bank)")
+            bank = mel_mrstft_bank(sample_rate, n_bins, resolutions)
+        self._host_bank = bank
+        self.n_bins = len(bank[0][0])
+        self._bank = None
+        super().__init__(y, resolutions, "lr")
+
+    def _device_bank(self):
+        if self._bank is None:
+            self._bank = _DeviceMelBank(self._host_bank, self.table.device)
+        return self._bank
+
+    def _table_floats(self) -> int:
+        return _hip.lib().stito_mrstft_table_floats_mel(self.res, self.n_res, self.n_bins, self.n_targets * self.channels, self.n)
+
+    def _fill(self, y: torch.Tensor) -> None:
+        _hip.check(_hip.lib().stito_mrstft_target_mel(self.res, self.n_res, self._device_bank().ref, _hip.ptr(y),
+                                                      self.n_targets * self.channels, self.n, _hip.ptr(self.table), _hip.stream_ptr()))
+
+    def _loss_calls(self):
+        L = _hip.lib()
+        return L.stito_mrstft_loss_mel, L.stito_mrstft_loss_slots_mel, (self._device_bank().ref,)
+
+
+def compute_mel_mrstft_distance(x: torch.Tensor, y: torch.Tensor, sample_rate, n_bins: int = MEL_MRSTFT_BINS,
+                                resolutions=None) -> torch.Tensor:
+    """auraloss.freq.MultiResolutionSTFTLoss(scale="mel", n_bins=n_bins, sample_rate=sample_rate)(x[b], y[b]) per item (restated,
+    unpinned) -> (B,) float32 on x's device, with compute_mrstft_distance's shape rules: the magnitudes of every frame are summed
+    into n_bins Slaney mel bands before the spectral convergence and the log-magnitude term are taken, so the near-silent bins
+    above a few kHz no longer carry the loss.  ValueError, before anything touches the GPU, for a bank with an empty band."""
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("expected (bs, chs, seq_len)")
+    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    bank = mel_mrstft_bank(sample_rate, n_bins, resolutions)
+    _mrstft_check_length(x.shape[-1], resolutions)
+    xin, dev = _gpu(x)
+    yin = y.detach().to(dev, torch.float32).contiguous()
+    return MelMrstftTarget(yin, resolutions=resolutions, bank=bank).loss(xin).to(x.device)

@@ -410,7 +410,7 @@ def run_es(
     update rule, the library's own random stream: NOT the trajectory the host ES walks from the same seed.  Single rank only and no
     savepop; max_iters must be at least 1 (the host ES accepts 0); find_w0 is the host-drawn population it always was.  NaN
     warnings are printed once per batch, for all of its passes."""
-    _check_distance(distance)
+    _check_distance(distance, sample_rate)
     if device_es:
         _check_device_es(plugins, popsize, max_iters, savepop, sync_every)
     if content_model is not None and content_embed_func is None:
@@ -486,13 +486,20 @@ def _check_device_es(plugins, popsize, max_iters, savepop, sync_every):
     cma.device_es_state_bytes(sum(plugin["num_params"] for plugin in plugins.values()), popsize, max_iters)
 
 
-# the objectives that compare the rendered AUDIO with the target's: "mrstft" channel by channel, "mrstft-sd" on [L + R, L - R]
-_AUDIO_DISTANCES = ("mrstft", "mrstft-sd")
+# the objectives that compare the rendered AUDIO with the target's: "mrstft" channel by channel, "mrstft-sd" on [L + R, L - R],
+# "mrstft-mel" channel by channel on mel-band sums of the magnitudes
+_AUDIO_DISTANCES = ("mrstft", "mrstft-sd", "mrstft-mel")
 
 
-def _check_distance(distance):
+def _check_distance(distance, sample_rate=None):
+    """The name -- and, under "mrstft-mel", the bank of the sample rate, built on the host: a band with no bin is a ValueError
+    here, before an input is normalised or anything launched."""
     if distance != "cosine" and distance not in _AUDIO_DISTANCES:
         raise ValueError(f"Unknown distance: {distance}")
+    if distance == "mrstft-mel":
+        from . import features
+
+        features.mel_mrstft_bank(sample_rate)
 
 
 def _check_mrstft_pairs(input_audios, target_audios, plugins, target="target {b}", chain="the chain", distance="mrstft"):
@@ -522,12 +529,14 @@ def _check_mrstft_savepop(savepop, distance="mrstft"):
 
 def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
     """The one place that turns `distance` into an evaluator, both resolved through `engine` when called.  target: the target
-    embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft" and
-    "mrstft-sd", which embed nothing and launch eagerly: kw has nothing to say to them)."""
+    embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft",
+    "mrstft-sd" and "mrstft-mel", which embed nothing and launch eagerly: kw has nothing to say to them)."""
     if distance == "mrstft":
         return engine.MrstftEvaluator(x, sample_rate, plugins, target)
     if distance == "mrstft-sd":
         return engine.MrstftEvaluator(x, sample_rate, plugins, target, stereo="sum-diff")
+    if distance == "mrstft-mel":
+        return engine.MelMrstftEvaluator(x, sample_rate, plugins, target)
     return engine.PopulationEvaluator(x, sample_rate, plugins, model, target, **kw)
 
 
@@ -676,8 +685,9 @@ def run_staged_es(
     distance="mrstft": every stage scores its sub-chain's render against the full target AUDIO with an engine.MrstftEvaluator
     (model and embed_func may be None, nothing is embedded); everything else is as above.  Every stage's sub-chain must
     render the target's channel count, and savepop is refused as run_es refuses it for this objective.  distance="mrstft-sd"
-    is the same with the sum / difference distance: every stage's sub-chain must render 2 channels."""
-    _check_distance(distance)
+    is the same with the sum / difference distance: every stage's sub-chain must render 2 channels; distance="mrstft-mel" is
+    distance="mrstft" on mel-band sums of the magnitudes (engine.MelMrstftEvaluator)."""
+    _check_distance(distance, sample_rate)
     savepop = bool(savepop or save_pop)
     names = list(plugins.keys())
     if distance in _AUDIO_DISTANCES:  # every stage compares its sub-chain's render with the full target
@@ -795,8 +805,11 @@ def run_es_batch(
     is built once, and pairs that stop drop out of it through the slot list of stito_mrstft_loss_slots.
 
     distance="mrstft-sd": the same on both forms and on every path of the list form, with the distance taken between the sums
-    and differences of the two channels (MrstftEvaluator(stereo="sum-diff")); the chain must render exactly 2 channels."""
-    _check_distance(distance)
+    and differences of the two channels (MrstftEvaluator(stereo="sum-diff")); the chain must render exactly 2 channels.
+
+    distance="mrstft-mel": the same again with the distance taken between 64 mel-band sums of the magnitudes
+    (engine.MelMrstftEvaluator), channels compared L/R; any channel count the chain renders."""
+    _check_distance(distance, sample_rate)
     ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
     if ragged:
         input_audios, target_audios = _check_ragged_pairs(input_audios, target_audios)
