@@ -230,6 +230,11 @@ def stream_ptr():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def scratch(nbytes: int, device, ws=None, name: str = ""):
+    """Scratch of one launch sequence: the engine.Workspace `ws`'s buffer of that name, else this call's own, in the stream's order."""
+    return ws.get(name, nbytes, device) if ws is not None else torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
 def mel_tables(melW, dev):
     """Device tables of a (n_bins, n_mels) mel filterbank for stito_frontend: every band is one run of consecutive
     non-zero bins.  -> (mel_start, mel_len, mel_off, mel_w, mel_w_stride) in the interleaved layout: weight i of band m

@@ -203,8 +203,8 @@ def chain_out_channels(plugins: Dict[str, dict], in_channels: int) -> int:
     return c
 
 
-class _Workspace:
-    """Grow-only device scratch buffers keyed by name (torch owns the memory)."""
+class Workspace:
+    """Grow-only device scratch buffers keyed by name (torch owns the memory), one per evaluator; a call handed none: _hip.scratch."""
 
     def __init__(self):
         self._bufs: Dict[str, torch.Tensor] = {}
@@ -212,20 +212,20 @@ class _Workspace:
     def get(self, name: str, nbytes: int, device) -> torch.Tensor:
         b = self._bufs.get(name)
         if b is None or b.numel() < nbytes or b.device != device:
-            b = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-            self._bufs[name] = b
+            b = self._bufs[name] = _hip.scratch(nbytes, device)
         return b
 
-
-_WS = _Workspace()
+    def buffers(self) -> Tuple[torch.Tensor, ...]:
+        """The buffers held at this moment: what a captured graph pins (a later, larger get() replaces the entry, not this object)."""
+        return tuple(self._bufs.values())
 
 
 def render_population(plugins: Dict[str, dict], x: torch.Tensor, W: torch.Tensor, sample_rate: float,
-                      chain=None, out=None, ws_key: str = "render") -> Tuple[torch.Tensor, torch.Tensor]:
+                      chain=None, out=None, ws: Optional[Workspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """x (C, L) float32 on the GPU -- or (B, C, L): B inputs, candidate p reads input p // (P // B) --
     W (P, D) float64 on the GPU -> (audio (P, C', L) before peak normalisation, peaks (P,)).
-    out: (audio, peaks) to render into (contiguous slices of a larger population's buffers); ws_key: name of the
-    workspace this call uses (two renders in flight on different streams need different ones)."""
+    out: (audio, peaks) to render into (contiguous slices of a larger population's buffers); ws: the evaluator's Workspace the
+    render's scratch comes from (None: allocated for this call on the current stream)."""
     _hip.require_gpu()
     L = _hip.lib()
     descs, ndims = chain if chain is not None else compile_chain(plugins)
@@ -260,10 +260,10 @@ def render_population(plugins: Dict[str, dict], x: torch.Tensor, W: torch.Tensor
                 if hasattr(descs, "_keep"):
                     descs._keep.append(t)
     need = L.stito_render_workspace_bytes(descs, n_fx, C, n, P)
-    ws = _WS.get(ws_key, need, x.device)
+    buf = _hip.scratch(need, x.device, ws, "render")
     _hip.check(L.stito_render_population_multi(descs, n_fx, _hip.ptr(x), n_inputs, C, n, _hip.ptr(W), P, ndims,
-                                               float(sample_rate), _hip.ptr(audio), _hip.ptr(peaks), _hip.ptr(ws),
-                                               ws.numel(), _hip.stream_ptr()))
+                                               float(sample_rate), _hip.ptr(audio), _hip.ptr(peaks), _hip.ptr(buf),
+                                               buf.numel(), _hip.stream_ptr()))
     return audio, peaks
 
 
@@ -320,6 +320,7 @@ class _Evaluator:
         self.n_inputs = x.shape[0]
         self.x_full = x.to(self.device, torch.float32).contiguous()
         self._x_padded = None  # cut_to_span's zero-padded copy of x_full
+        self.ws = Workspace()  # the persistent scratch of this evaluator's launches: one evaluator, one stream at a time
         self.rendered_candidates = 0
 
     def _pairs(self, pairs, what: str = "inputs", once: bool = False) -> List[int]:
@@ -439,6 +440,7 @@ class PopulationEvaluator(_Evaluator):
         self.capture_after = int(os.environ.get("STITO_GRAPH_AFTER", "32")) if capture_after is None else int(capture_after)
         self._graph_calls = {}
         self._graph_evictions = 0
+        self._n_flag_rows = 0  # rows of self.flags the last evaluate() wrote
         self._graphs = {}      # (P, input pointer, input shape) -> (graph, W buffer, loss, mid, side, n_calls, buffers kept alive)
 
     def _input(self, random_crop: bool, rng, parallel: bool = False) -> torch.Tensor:
@@ -461,8 +463,8 @@ class PopulationEvaluator(_Evaluator):
         L = _hip.lib()
         (b0, b1), spans = self._spans(p0, p1, per, pairs)
         xin = x[0] if x.shape[0] == 1 else x[b0:b1]
-        audio, peaks = render_population(self.plugins, xin, Wc, self.sample_rate, chain=self.chain)
-        mid, side = self.model.embed_raw(audio, peaks, norm_passes=2)
+        audio, peaks = render_population(self.plugins, xin, Wc, self.sample_rate, chain=self.chain, ws=self.ws)
+        mid, side = self.model.embed_raw(audio, peaks, norm_passes=2, ws=self.ws)
         loss = torch.empty(mid.shape[0], dtype=torch.float32, device=self.device)
         # dropout (style_transfer.py:549-551) hits the embeddings only inside the distance; the cosine is
         # scale-invariant, so dropping the raw vectors and normalising afterwards is the same quantity.
@@ -529,9 +531,9 @@ class PopulationEvaluator(_Evaluator):
                 torch.cuda.synchronize(self.device)
                 return None
             torch.cuda.current_stream(self.device).wait_stream(cap_stream)
-            # the graph holds raw pointers: everything it touches stays referenced here -- the outputs, the render and trunk
-            # workspaces as they were at capture (a later, larger call replaces those objects; the graph keeps its own)
-            keep = (keep, _WS._bufs.get("render"), getattr(self.model, "_ws", None), x)
+            # the graph holds raw pointers: everything it touches stays referenced here -- the outputs, the input and this
+            # evaluator's scratch as it was at capture (a later, larger call replaces those buffers; the graph keeps its own)
+            keep = (keep, self.ws.buffers(), x)
             ent = (g, Wbuf, loss, mid, side, n_calls, keep)
             if len(self._graphs) >= 4:   # a few shapes at most (find_w0 batch, population, last partial shard)
                 old = next(iter(self._graphs))
@@ -586,7 +588,7 @@ class PopulationEvaluator(_Evaluator):
             else:
                 (b0, b1), spans = self._spans(p0, p1, per, pairs)
                 xin = x[0] if B == 1 else x[b0:b1]
-                audio, peaks = render_population(self.plugins, xin, Wc, self.sample_rate, chain=self.chain)
+                audio, peaks = render_population(self.plugins, xin, Wc, self.sample_rate, chain=self.chain, ws=self.ws)
                 loss, emb = self._generic_loss(normalize_audio_(audio, peaks), spans, dropout)
                 generic_embeds.append(emb)
             losses.append(loss)
@@ -629,7 +631,7 @@ class PopulationEvaluator(_Evaluator):
         return loss, out
 
     def nan_flags(self) -> Optional[torch.Tensor]:
-        return self.flags[: getattr(self, "_n_flag_rows", 0)].sum(dim=0)
+        return self.flags[: self._n_flag_rows].sum(dim=0)
 
     def nan_warning(self, flags: Optional[torch.Tensor] = None) -> Optional[str]:
         """The reference's "Warning: NaNs found in ..._embeddings" (utils.py:491-497) for the last evaluate() -- or for the
@@ -773,9 +775,9 @@ class MrstftEvaluator(_Evaluator):
                     raise ValueError(f"pairs {pairs}: the static table of {length} samples holds the targets of {sorted(slot_of)}")
                 slots = torch.tensor([slot_of[b] for b in pairs], dtype=torch.int32).to(self.device)
         Wt = self._on_device(Wn)
-        audio, peaks = render_population(self.plugins, x[0] if x.shape[0] == 1 else x, Wt, self.sample_rate, chain=self.chain)
+        audio, peaks = render_population(self.plugins, x[0] if x.shape[0] == 1 else x, Wt, self.sample_rate, self.chain, ws=self.ws)
         self.rendered_candidates += Wn.shape[0]
-        loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots)
+        loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots, ws=self.ws)
         return loss, {}, (normalize_audio_(audio, peaks) if want_audio else None)
 
 

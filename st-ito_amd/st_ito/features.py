@@ -164,10 +164,8 @@ def compute_barkspectrum(x: torch.Tensor, fft_size: int = 32768, n_bands: int = 
         _hip.check(L.stito_barkspectrum(_hip.ptr(xin), bs, chs, n, _MODES[mode], fft_size, _hip.ptr(_twiddle(fft_size, dev)),
                                         _hip.ptr(_cache[key]), n_bands, _hip.ptr(out), _hip.stream_ptr()))
     else:
-        from .engine import _WS
-
         tables = _mixed_tables(fft_size, dev)
-        ws = _WS.get("bark_mixed", L.stito_barkspectrum_mixed_workspace_bytes(bs, n_sig, fft_size), dev)
+        ws = _hip.scratch(L.stito_barkspectrum_mixed_workspace_bytes(bs, n_sig, fft_size), dev)
         _hip.check(L.stito_barkspectrum_mixed(_hip.ptr(xin), bs, chs, n, _MODES[mode], fft_size, _hip.ptr(tables), tables.shape[0],
                                               _hip.ptr(_cache[key]), n_bands, _hip.ptr(out), _hip.ptr(ws), ws.numel(),
                                               _hip.stream_ptr()))
@@ -336,21 +334,20 @@ class MrstftTarget:
         self._fill(y.contiguous())
         return self
 
-    def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None) -> torch.Tensor:
+    def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None, ws=None) -> torch.Tensor:
         """audio (P, C, n) float32 on the GPU, P a multiple of the number of targets (candidate p against target p // (P // T))
         -> (P,) float32.  norm_passes 1: audio[p] / clip(peaks[p], 1e-8) is what gets scored, folded into the kernel's loader.
         slots: (K,) int32 on the GPU, P a multiple of K -- the K stacked populations are scored against the targets slots[k] of
         the table (stito_mrstft_loss_slots: any subset, any order; a slot that names no target gives NaN).  A sum / difference
-        table goes through the _sd entry points, same arguments."""
-        from .engine import _WS
-
+        table goes through the _sd entry points, same arguments.  ws: the evaluator's engine.Workspace the kernels' scratch comes
+        from (None: allocated for this call on the current stream)."""
         if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
             raise ValueError(f"audio must be (P, {self.channels}, {self.n}), got {tuple(audio.shape)}")
         assert audio.is_cuda and audio.dtype == torch.float32
         audio = audio.contiguous()
         P = audio.shape[0]
         L = _hip.lib()
-        ws = _WS.get("mrstft", L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device)
+        ws = _hip.scratch(L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device, ws, "mrstft")
         out = torch.empty(P, dtype=torch.float32, device=audio.device)
         plain, with_slots, between = self._loss_calls()
         if slots is None:

@@ -174,8 +174,6 @@ class Cnn14(nn.Module):
         self.fc_side.bias.data.fill_(0.0)
 
         self._packed = None      # device-side packed weights, built lazily
-        self._packed_key = None
-        self._ws = None
         self.max_streams_per_pass = int(os.environ.get("STITO_MAX_STREAMS", "512"))
         k = conv_knobs()   # the knobs of the packing rule: read in prepare(), so they may be set on the model until then
         self.conv_algo, self.conv_pre_min_cout, self.conv_f2reg, self.conv_fuse1 = k.conv_algo, k.conv_pre_min_cout, k.conv_f2reg, k.conv_fuse1
@@ -299,11 +297,8 @@ class Cnn14(nn.Module):
             self.prepare()
         return self._packed
 
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != self._device():
-            self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self._device())
-        return self._ws
+    def _workspace(self, nbytes: int, ws=None) -> torch.Tensor:  # the caller's engine.Workspace's, else this call's own
+        return _hip.scratch(nbytes, self._device(), ws, "trunk")
 
     # ------------------------------------------------------------------------------------
     def logmel(self, audio: torch.Tensor, peaks: Optional[torch.Tensor] = None, norm_passes: int = 0,
@@ -323,8 +318,8 @@ class Cnn14(nn.Module):
         _hip.check(L.stito_logmel(FE, _hip.ptr(audio), _hip.ptr(peaks), norm_passes, B, C, n, _hip.ptr(out), _hip.stream_ptr()))
         return out
 
-    def trunk(self, logmel: torch.Tensor, n_cand: int, channels: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """log-mel (n_cand*channels, T, M) -> raw (mid, side) fc outputs (panns.py:250-281)."""
+    def trunk(self, logmel: torch.Tensor, n_cand: int, channels: int, ws=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """log-mel (n_cand*channels, T, M) -> raw (mid, side) fc outputs (panns.py:250-281); ws: the caller's engine.Workspace."""
         W, FE, _ = self._ensure()
         L = _hip.lib()
         T = logmel.shape[1]
@@ -332,14 +327,14 @@ class Cnn14(nn.Module):
         mid = torch.empty((n_cand, self.embed_dim), dtype=torch.float32, device=dev)
         side = torch.empty((n_cand, self.embed_dim), dtype=torch.float32, device=dev)
         need = L.stito_cnn14_workspace_bytes(W, n_cand * channels, T)
-        ws = self._workspace(need)
+        buf = self._workspace(need, ws)
         _hip.check(L.stito_cnn14_forward(W, _hip.ptr(logmel), n_cand, channels, T, _hip.ptr(mid), _hip.ptr(side),
-                                         _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
+                                         _hip.ptr(buf), buf.numel(), _hip.stream_ptr()))
         return mid, side
 
-    def embed_raw(self, audio: torch.Tensor, peaks: Optional[torch.Tensor], norm_passes: int):
+    def embed_raw(self, audio: torch.Tensor, peaks: Optional[torch.Tensor], norm_passes: int, ws=None):
         """audio (B, C, L) on the GPU (+ per-item peaks) -> raw (mid, side), sub-batched so that the
-        activation workspace stays bounded."""
+        activation workspace stays bounded.  ws: as trunk()."""
         audio = audio.contiguous()
         B, C, _ = audio.shape
         step = max(1, self.max_streams_per_pass // C)
@@ -348,7 +343,7 @@ class Cnn14(nn.Module):
             a = audio[b0:b0 + step]
             p = peaks[b0:b0 + step].contiguous() if peaks is not None else None
             lm = self.logmel(a, p, norm_passes)
-            m, s = self.trunk(lm, a.shape[0], C)
+            m, s = self.trunk(lm, a.shape[0], C, ws)
             mids.append(m); sides.append(s)
         return (torch.cat(mids), torch.cat(sides)) if len(mids) > 1 else (mids[0], sides[0])
 

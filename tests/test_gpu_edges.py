@@ -56,8 +56,8 @@ def test_error_paths(dev, pm):
 
 
 def test_part_populations_into_one_buffer_on_two_streams_are_the_single_call(dev):
-    """render_population(out=, ws_key=): two half populations rendered into slices of one buffer, each on its own HIP stream with its
-    own workspace (what tools/render_split_bench.py times), give bitwise the audio and peaks of one call."""
+    """render_population(out=): two half populations rendered into slices of one buffer, each on its own HIP stream with the
+    workspace allocated per call on that stream (what tools/render_split_bench.py times), give bitwise the audio and peaks of one call."""
     from st_ito import effects as E, engine
     pp = E.make_plugins("bench5")
     chain = engine.compile_chain(pp, False)
@@ -70,7 +70,7 @@ def test_part_populations_into_one_buffer_on_two_streams_are_the_single_call(dev
     for i, (p0, p1) in enumerate(((0, 2), (2, 6))):
         streams[i].wait_stream(main)
         with torch.cuda.stream(streams[i]):
-            engine.render_population(pp, x, W[p0:p1], SR, chain=chain, out=(audio[p0:p1], peaks[p0:p1]), ws_key=f"render_part{i}")
+            engine.render_population(pp, x, W[p0:p1], SR, chain=chain, out=(audio[p0:p1], peaks[p0:p1]))
     for s in streams:
         main.wait_stream(s)
     torch.cuda.synchronize()

@@ -334,6 +334,74 @@ def test_graph_capture_failure_falls_back_to_eager_and_evicted_shapes_do_not_thr
     assert set(ev3._graphs) == keys
 
 
+_TWO_STREAM_RUNS = {}
+
+
+def _two_stream_run(dev, graph):
+    """Three evaluators that own their scratch, driven on two side streams with nothing between the calls: A (bench5, stereo, 65536
+    samples, population 2; graph: replaying a hipGraph captured on its first call) on stream 1, B (the same on the same model,
+    population 3: larger render and trunk workspaces) on stream 2, C (MRSTFT objective, 8192 samples, population 4) on stream 1 --
+    three rounds.  The references are one eager call each of a fresh evaluator on the default stream.  Every call's loss, and A's
+    and B's embeddings, must be bitwise the reference.  -> (A, B, C), run once per `graph`."""
+    if graph in _TWO_STREAM_RUNS:
+        return _TWO_STREAM_RUNS[graph]
+    from st_ito import effects as E
+    from st_ito.engine import MrstftEvaluator, PopulationEvaluator
+    from st_ito.utils import get_param_embeds, make_synthetic_param_model
+    pm = make_synthetic_param_model(0)
+    pp = E.make_plugins("bench5")
+    x, xs, ys = O.synth_audio(61, 2, 65536)[None], O.synth_audio(63, 2, 8192)[None], O.synth_audio(64, 2, 8192)[None]
+    te = get_param_embeds(O.synth_audio(62, 2, 65536)[None], pm, SR)
+    rng = np.random.default_rng(6)
+    Ws = [torch.from_numpy(rng.random((P, 45))).to(dev) for P in (2, 3, 4)]   # on the device: no upload between the calls
+
+    def make(**graph_a):
+        return (PopulationEvaluator(x, SR, pp, pm, te, **graph_a), PopulationEvaluator(x, SR, pp, pm, te, use_graph=False),
+                MrstftEvaluator(xs, SR, pp, ys))
+
+    refs = [ev.evaluate(W, parallel=True)[:2] for ev, W in zip(make(use_graph=False), Ws)]
+    torch.cuda.synchronize()
+    evs = make(use_graph=True, capture_after=0) if graph else make(use_graph=False)
+    main = torch.cuda.current_stream(dev)
+    s1, s2 = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    s1.wait_stream(main); s2.wait_stream(main)
+    got = []
+    for _ in range(3):
+        for k, s in ((0, s1), (1, s2), (2, s1)):
+            with torch.cuda.stream(s):
+                got.append((k, evs[k].evaluate(Ws[k], parallel=True)[:2]))
+    main.wait_stream(s1); main.wait_stream(s2)
+    torch.cuda.synchronize()
+    assert len(got) == 9
+    for i, (k, (loss, emb)) in enumerate(got):
+        assert torch.equal(loss, refs[k][0]), f"call {i}, evaluator {'ABC'[k]}: loss"
+        assert sorted(emb) == sorted(refs[k][1]) == ([] if k == 2 else ["mid", "side"])
+        for name in emb:
+            assert torch.equal(emb[name], refs[k][1][name]), f"call {i}, evaluator {'ABC'[k]}: {name}"
+    _TWO_STREAM_RUNS[graph] = evs
+    return evs
+
+
+def test_two_evaluators_on_two_streams_give_each_ones_own_bits(dev):
+    """Eager launches only: two evaluators of different population on one model, and a third of the other objective, interleaved
+    on two streams without a synchronisation, each return the bits they return alone (_two_stream_run)."""
+    A, B, C = _two_stream_run(dev, graph=False)
+    assert not A._graphs and not B._graphs
+
+
+def test_two_evaluators_on_two_streams_one_replaying_a_graph(dev):
+    """The same interleaving with A replaying its captured graph (capture_after=0) while B launches eagerly on the other stream."""
+    A, B, C = _two_stream_run(dev, graph=True)
+    assert len(A._graphs) == 1 and not B._graphs
+
+
+def test_evaluators_hold_disjoint_workspaces(dev):
+    """After the interleaved run every evaluator holds its own buffers (render + trunk, render + mrstft): no address twice."""
+    evs = _two_stream_run(dev, graph=False)
+    ptrs = [b.data_ptr() for ev in evs for b in ev.ws.buffers()]
+    assert [len(ev.ws.buffers()) for ev in evs] == [2, 2, 2] and len(set(ptrs)) == 6, ptrs
+
+
 def test_graph_replay_soak_in_fresh_processes(dev):
     """the captured evaluate step against the eager launches, bit for bit, over 50 FRESH processes x 20 replays
     with new parameters each (tools/graph_soak.py; the corruption of round 4 showed in every process from the second

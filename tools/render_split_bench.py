@@ -33,7 +33,7 @@ def split():
         s.wait_stream(main)
     for i, (p0, p1) in enumerate(bounds):
         with torch.cuda.stream(streams[i]):
-            engine.render_population(plugins, x, W[p0:p1], SR, chain=chain, out=(audio[p0:p1], peaks[p0:p1]), ws_key=f"render{i}")
+            engine.render_population(plugins, x, W[p0:p1], SR, chain=chain, out=(audio[p0:p1], peaks[p0:p1]))
     for s in streams:
         main.wait_stream(s)
 

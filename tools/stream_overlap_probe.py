@@ -43,15 +43,15 @@ for chain in ("Compressor", "Reverb", "ParametricEQ", "ParametricEQ,Compressor,R
         engine.render_population(plugins, x, W, SR, chain=ch, out=full)
 
     def serial():
-        engine.render_population(plugins, x, W[:h], SR, chain=ch, out=outs[0], ws_key="pa")
-        engine.render_population(plugins, x, W[h:], SR, chain=ch, out=outs[1], ws_key="pb")
+        engine.render_population(plugins, x, W[:h], SR, chain=ch, out=outs[0])
+        engine.render_population(plugins, x, W[h:], SR, chain=ch, out=outs[1])
 
     def overlapped():
         main = torch.cuda.current_stream()
-        for s, wsl, o, key in ((s1, W[:h], outs[0], "pa"), (s2, W[h:], outs[1], "pb")):
+        for s, wsl, o in ((s1, W[:h], outs[0]), (s2, W[h:], outs[1])):
             s.wait_stream(main)
             with torch.cuda.stream(s):
-                engine.render_population(plugins, x, wsl, SR, chain=ch, out=o, ws_key=key)
+                engine.render_population(plugins, x, wsl, SR, chain=ch, out=o)
         main.wait_stream(s1); main.wait_stream(s2)
 
     print(f"{chain:50s} pop {a.pop}: one launch set {timed(one):7.3f} ms | two halves, one stream {timed(serial):7.3f} ms | two halves, two streams {timed(overlapped):7.3f} ms")
