@@ -112,7 +112,9 @@ int stito_version(void);
  * stito_barkspectrum_mixed_workspace_bytes, stito_fft_mixed_plan; 4 = stito_mrstft_table_floats, stito_mrstft_target,
  * stito_mrstft_workspace_bytes, stito_mrstft_loss; 5 = stito_mrstft_loss_slots; 6 = the device-resident CMA-ES, stito_cmaes_*;
  * 7 = stito_mrstft_target_sd, stito_mrstft_loss_sd, stito_mrstft_loss_slots_sd; 8 = stito_mel_bank, stito_mrstft_table_floats_mel,
- * stito_mrstft_target_mel, stito_mrstft_loss_mel, stito_mrstft_loss_slots_mel. */
+ * stito_mrstft_target_mel, stito_mrstft_loss_mel, stito_mrstft_loss_slots_mel; 9 = the prefiltered MR-STFT distances,
+ * stito_mrstft_table_floats_pf, stito_mrstft_workspace_bytes_pf, stito_mrstft_target_pf, stito_mrstft_loss_pf,
+ * stito_mrstft_loss_slots_pf. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -617,6 +619,38 @@ int stito_mrstft_loss_slots_mel(const int *res, int n_res, const stito_mel_bank 
                                 int norm_passes, const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots,
                                 int pop, int channels, int64_t n_samples, float *loss_dev, void *workspace_dev,
                                 size_t workspace_bytes, void *stream);
+
+/* The prefiltered variants (ABI 10.9): the three distances above on rows that went through an FIR first -- auraloss's
+ * perceptual_weighting=True (its 101-tap A-weighting FIR; restated, PARITY UNPINNED) or any other pre-emphasis.  taps_dev: n_taps
+ * float32 on the device, n_taps odd in [1, 255], centre c = n_taps / 2.  A row x of n samples becomes
+ *     p[i] = sum_{k < n_taps} taps[k] x[i + k - c],  0 <= i < n,  x = 0 outside [0, n)
+ * -- torch.nn.functional.conv1d(x, taps, padding=c): cross-correlation, zero padding, same length.  Order: the peak normalisation
+ * of norm_passes, under kind 1 the rows [L + R, L - R], the prefilter, then everything the unfiltered call does, applied to p: the
+ * STFT's reflect padding reflects the FILTERED row.  The table side goes through the same steps.  Every p[i] is a chain of fmaf in
+ * tap order from 0.0f, in the table kernel and in the candidate kernel alike, so loss(y, table_pf(y)) is exactly 0 and a candidate's
+ * loss has the same bits at every position of every batch and under every slot list.  The filter runs in the kernel's loader, on
+ * the tile's samples in LDS: no filtered copy of the population exists in memory.
+ * kind: 0 the L/R distance (stito_mrstft_loss), 1 sum / difference (stito_mrstft_loss_sd; channels must be 2), 2 mel
+ * (stito_mrstft_loss_mel; `bank` as there).  bank must be NULL unless kind is 2.  After (kind, bank, taps_dev, n_taps) the arguments
+ * are those of the unfiltered calls; stito_mrstft_target_pf takes (n_targets, channels) like stito_mrstft_target_sd and writes
+ * n_targets * channels rows.  stito_mrstft_loss_pf is stito_mrstft_loss_slots_pf with the identity map.  The table does not record
+ * the taps: the same taps (and bank) must be given to the table call and to the loss call.
+ * The prefiltered kernels need more LDS and bound a tile's span, so their tiling may differ from the unfiltered kernels': table and
+ * workspace have their OWN size functions, stito_mrstft_table_floats_pf (n_bins: the bank's under kind 2, else 0) and
+ * stito_mrstft_workspace_bytes_pf, which return 0 for arguments the launches refuse.
+ * STITO_E_INVALID, naming the value, before any device is asked: kind outside 0 .. 2, n_taps even or outside [1, 255], null
+ * taps_dev, a missing bank under kind 2 or a bank under the other kinds, channels other than 2 under kind 1. */
+int64_t stito_mrstft_table_floats_pf(int kind, int n_bins, int n_taps, const int *res, int n_res, int rows, int64_t n_samples);
+size_t stito_mrstft_workspace_bytes_pf(int kind, int n_taps, const int *res, int n_res, int pop, int channels, int64_t n_samples);
+int stito_mrstft_target_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                           const float *y_dev, int n_targets, int channels, int64_t n_samples, float *table_dev, void *stream);
+int stito_mrstft_loss_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                         const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets, int pop,
+                         int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int stito_mrstft_loss_slots_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                               const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
+                               const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples, float *loss_dev,
+                               void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

@@ -33,6 +33,16 @@
 // order, with NO extra LDS.  Then lane l owns the bands l, l + 64, ...: one banded dot product each, a chain of explicit fmas in
 // bin order over the interleaved weights (weight j of band m at w[j * stride + m]: the lanes read consecutive floats per step).
 // The table holds frames x n_bins mel magnitudes per (row, resolution) and sum M_y^2; sums, tile tree and final launch are shared.
+//
+// The prefiltered variants (template PRE; auraloss's perceptual_weighting=True, restated, and any other odd-length FIR) put one stage
+// into the loader of each of the three: p[i] = sum_k taps[k] x[i + k - c], c = n_taps / 2, x zero outside the row -- conv1d with
+// zero padding -- on the normalised (and, under SD, combined) row, and everything behind the loader sees p: the STFT's reflect
+// padding reflects the FILTERED row.  The reflected sample indices of a tile's span form one contiguous run [s_min, s_max] of the
+// row, so the workgroup stages the raw run [s_min - c, s_max + c] where the span will lie, every thread filters runs of four
+// consecutive outputs from a sliding register window (16 fmas per four new samples from LDS; the taps, the same for every lane,
+// come through scalar loads; the chain of each output is fmaf in tap order from 0.0f), keeps them in registers across a barrier,
+// writes them over the raw run, and a second register pass lays the span out through the reflection.  LDS grows by the filter's
+// reach (256 floats), not by a second span.
 #include "common.h"
 
 #include <type_traits>
@@ -42,6 +52,12 @@ namespace stito {
 static constexpr int MR_THREADS = 256, MR_WAVES = MR_THREADS / 64;
 static constexpr int MR_MAX_RES = 8;
 static constexpr int MR_MAX_CH = 8;  // the final sum gives one lane of a wave to every (resolution, channel)
+// The prefilter: up to 255 taps, taken in blocks of four, so the raw run reaches MR_PF_REACH samples past its last whole float4; a
+// thread filters MR_PF_GROUPS runs of four outputs and holds them in registers, so a prefiltered tile's span has at most
+// MR_PF_MAX_SPAN samples (the plan picks F accordingly).
+static constexpr int MR_PF_MAX_TAPS = 255, MR_PF_REACH = 256;
+static constexpr int MR_PF_GROUPS = 8;
+static constexpr int MR_PF_MAX_SPAN = 4 * MR_PF_GROUPS * MR_THREADS;
 
 // Everything the launches of one (resolutions, n) need, worked out once on the host: frames, tiles, LDS, and where the
 // pieces of the table and of the workspace lie.  Table (floats; every offset even, so doubles and float2 are aligned):
@@ -58,15 +74,18 @@ struct MrPlan {
     int64_t row_floats, mags_base, tiles_total;
 };
 
-static size_t mr_lds_bytes(int N, int hop, int F) {
+static size_t mr_lds_bytes(int N, int hop, int F, bool pre = false) {
     // tile sums (2 x MR_THREADS doubles) + one FFT buffer per wave + twiddles + window + sample span
-    return (size_t)2 * MR_THREADS * 8 + (size_t)MR_WAVES * (N / 2) * 8 + (size_t)(N / 2) * 8 + (size_t)N * 4 +
-           ((size_t)(F - 1) * hop + N) * 4;
+    const size_t plain = (size_t)2 * MR_THREADS * 8 + (size_t)MR_WAVES * (N / 2) * 8 + (size_t)(N / 2) * 8 + (size_t)N * 4 +
+                         ((size_t)(F - 1) * hop + N) * 4;
+    // prefiltered: the span rounded up to whole float4 and the filter's reach behind the raw run (whole tap blocks)
+    return pre ? plain + (size_t)(4 + MR_PF_REACH) * 4 : plain;
 }
 
 // n_bins: 0 for the linear table (a row of a frame is its n_fft / 2 + 1 bins), else the bands of the mel table.  The LDS, the
-// tiles and the workspace do not depend on it.
-static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p, int n_bins = 0) {
+// tiles and the workspace do not depend on it.  pre: the plan of the prefiltered kernels, whose LDS is larger and whose span is
+// bounded, so F, the tiles and with them the table's scratch and the workspace may differ from the plain plan's.
+static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p, int n_bins = 0, bool pre = false) {
     STITO_REQUIRE(res != nullptr, STITO_E_INVALID, "mrstft: null resolutions");
     STITO_REQUIRE(n_res >= 1 && n_res <= MR_MAX_RES, STITO_E_INVALID, "mrstft: %d resolutions, 1 .. %d are supported", n_res, MR_MAX_RES);
     // gfx950's LDS per workgroup: the plan also sizes the table and the workspace, so it asks no device (mr_device_fits does)
@@ -90,14 +109,16 @@ static int mr_plan(const int *res, int n_res, int64_t n, MrPlan &p, int n_bins =
         static const int cand_F[] = {32, 28, 24, 20, 16, 12, 8, 4, 2, 1};
         int F = 0;
         for (size_t budget : {(size_t)80 * 1024, lds_cap}) {
-            for (int f : cand_F)
-                if (mr_lds_bytes(N, hop, f) <= budget && mr_lds_bytes(N, hop, f) <= lds_cap) { F = f; break; }
+            for (int f : cand_F) {
+                if (pre && (int64_t)(f - 1) * hop + N > MR_PF_MAX_SPAN) continue;
+                if (mr_lds_bytes(N, hop, f, pre) <= budget && mr_lds_bytes(N, hop, f, pre) <= lds_cap) { F = f; break; }
+            }
             if (F) break;
         }
         STITO_REQUIRE(F > 0, STITO_E_UNSUPPORTED, "mrstft: n_fft %d needs %zu bytes of LDS per workgroup, the device has %zu", N,
-                      mr_lds_bytes(N, hop, 1), lds_cap);
+                      mr_lds_bytes(N, hop, 1, pre), lds_cap);
         p.F[i] = F;
-        p.lds[i] = mr_lds_bytes(N, hop, F);
+        p.lds[i] = mr_lds_bytes(N, hop, F, pre);
         p.tiles[i] = (p.T[i] + F - 1) / F;
         p.hdr_off[i] = hdr; hdr += 2 * (int64_t)N;
         p.mag_off[i] = mag; mag += (p.T[i] * p.bins[i] + 1) / 2 * 2;
@@ -140,6 +161,13 @@ struct MrDevMel : MrDev {
     const float *w;
 };
 template <bool MEL> using MrDevOf = std::conditional_t<MEL, MrDevMel, MrDev>;
+
+// The prefiltered kernels' argument: the argument of their kind with the taps behind it.  The kernels without PRE keep theirs.
+template <class Base> struct MrDevPre : Base {
+    const float *taps;   // [n_taps], n_taps odd
+    int n_taps;
+};
+template <bool MEL, bool PRE> using MrArgOf = std::conditional_t<PRE, MrDevPre<MrDevOf<MEL>>, MrDevOf<MEL>>;
 
 __device__ __forceinline__ float2 mr_cmul(float2 a, float2 b) {  // explicit fmas: the file is built with -ffp-contract=off
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
@@ -261,14 +289,108 @@ __device__ __forceinline__ int mr_target_of(int64_t cand, int per_target, const 
     return (t >= 0 && t < n_targets) ? t : -1;
 }
 
+// The prefiltered loader.  span: room for the tile's largest span rounded up to whole float4 and MR_PF_REACH floats behind it
+// (mr_lds_bytes).  On return span[0 .. span_len) holds the reflected FILTERED samples; the caller's barrier
+// publishes them.  x, r1, row: as in the plain loader (SD: x is the item's channel 0 and the row's parity picks sum or difference).
+template <bool SD>
+__device__ __forceinline__ void mr_prefiltered_span(const float *__restrict__ x, int64_t n, float r1, int64_t row, const float *__restrict__ taps,
+                                                    int n_taps, float *span, int64_t s0, int span_len, int tid) {
+    // the taps are the same for every lane and nobody writes them: read through the constant address space they come as scalar
+    // loads into SGPRs and leave the LDS pipe to the samples
+    typedef const __attribute__((address_space(4))) float *ctaps_t;
+    ctaps_t ctaps = (ctaps_t)(uintptr_t)taps;
+    // the samples the span reflects to: [max(a, 0), min(b, n - 1)], 1 .. -a before the row's start, 2 (n - 1) - b .. n - 2 behind its end
+    const int c = n_taps >> 1;
+    const int64_t a = s0, b = s0 + span_len - 1;
+    int64_t s_min = a < 0 ? 0 : a, s_max = b < n ? b : n - 1;
+    if (a < 0 && -a > s_max) s_max = -a;
+    if (b >= n && 2 * (n - 1) - b < s_min) s_min = 2 * (n - 1) - b;
+    if (s_min < 0) s_min = 0;
+    if (s_max > n - 1) s_max = n - 1;
+    const int run_len = (int)(s_max - s_min + 1);                 // <= span_len: every sample of the run is some span index's
+    const int raw_len = ((run_len + 3) & ~3) + 4 * ((n_taps + 3) >> 2);
+    // the raw run [s_min - c, ...), zero outside the row: raw[j] = x[s_min - c + j], so p[s_min + o] = sum_k taps[k] raw[o + k]
+    for (int i = tid; i < raw_len; i += MR_THREADS) {
+        const int64_t s = s_min - c + i;
+        float v = 0.0f;
+        if (s >= 0 && s < n) {
+            if (SD) {
+                const float l = x[s] * r1, r = x[n + s] * r1;
+                v = (row & 1) ? l - r : l + r;
+            } else {
+                v = x[s] * r1;
+            }
+        }
+        span[i] = v;
+    }
+    __syncthreads();
+    // outputs 4 g .. 4 g + 3 of group g from the window raw[4 g + 4 kb .. + 7]; every output's chain runs k = 0 .. n_taps - 1
+    float out[MR_PF_GROUPS][4];
+    const int kb_full = n_taps >> 2, tail = n_taps & 3;           // n_taps is odd: 1 or 3 taps behind the whole blocks
+#pragma unroll
+    for (int gi = 0; gi < MR_PF_GROUPS; ++gi) {
+        const int g = tid + gi * MR_THREADS;
+        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+        if (4 * g < run_len) {
+            const float4 *rp = (const float4 *)span + g;
+            float4 lo = rp[0];
+            for (int kb = 0; kb < kb_full; ++kb) {
+                const float4 hi = rp[kb + 1];
+                const float4 t = make_float4(ctaps[4 * kb], ctaps[4 * kb + 1], ctaps[4 * kb + 2], ctaps[4 * kb + 3]);
+                a0 = fmaf(t.x, lo.x, a0); a1 = fmaf(t.x, lo.y, a1); a2 = fmaf(t.x, lo.z, a2); a3 = fmaf(t.x, lo.w, a3);
+                a0 = fmaf(t.y, lo.y, a0); a1 = fmaf(t.y, lo.z, a1); a2 = fmaf(t.y, lo.w, a2); a3 = fmaf(t.y, hi.x, a3);
+                a0 = fmaf(t.z, lo.z, a0); a1 = fmaf(t.z, lo.w, a1); a2 = fmaf(t.z, hi.x, a2); a3 = fmaf(t.z, hi.y, a3);
+                a0 = fmaf(t.w, lo.w, a0); a1 = fmaf(t.w, hi.x, a1); a2 = fmaf(t.w, hi.y, a2); a3 = fmaf(t.w, hi.z, a3);
+                lo = hi;
+            }
+            const float4 hi = rp[kb_full + 1];
+            float4 t = make_float4(ctaps[4 * kb_full], 0.0f, 0.0f, 0.0f);                  // no read behind the last tap
+            a0 = fmaf(t.x, lo.x, a0); a1 = fmaf(t.x, lo.y, a1); a2 = fmaf(t.x, lo.z, a2); a3 = fmaf(t.x, lo.w, a3);
+            if (tail == 3) {
+                t.y = ctaps[4 * kb_full + 1]; t.z = ctaps[4 * kb_full + 2];
+                a0 = fmaf(t.y, lo.y, a0); a1 = fmaf(t.y, lo.z, a1); a2 = fmaf(t.y, lo.w, a2); a3 = fmaf(t.y, hi.x, a3);
+                a0 = fmaf(t.z, lo.z, a0); a1 = fmaf(t.z, lo.w, a1); a2 = fmaf(t.z, hi.x, a2); a3 = fmaf(t.z, hi.y, a3);
+            }
+        }
+        out[gi][0] = a0; out[gi][1] = a1; out[gi][2] = a2; out[gi][3] = a3;
+    }
+    __syncthreads();  // the raw run has been read: p goes over it, p[s_min + o] at span[o]
+#pragma unroll
+    for (int gi = 0; gi < MR_PF_GROUPS; ++gi) {
+        const int g = tid + gi * MR_THREADS;
+        if (4 * g < run_len) ((float4 *)span)[g] = make_float4(out[gi][0], out[gi][1], out[gi][2], out[gi][3]);
+    }
+    __syncthreads();
+    // the span through the reflection (no edge repeat), again by way of registers: span index i = padded index s0 + i
+    float val[4 * MR_PF_GROUPS];
+#pragma unroll
+    for (int v = 0; v < 4 * MR_PF_GROUPS; ++v) {
+        const int i = tid + v * MR_THREADS;
+        val[v] = 0.0f;
+        if (i < span_len) {
+            int64_t s = s0 + i;
+            if (s < 0) s = -s;
+            if (s >= n) s = 2 * (n - 1) - s;
+            val[v] = span[s - s_min];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int v = 0; v < 4 * MR_PF_GROUPS; ++v) {
+        const int i = tid + v * MR_THREADS;
+        if (i < span_len) span[i] = val[v];
+    }
+}
+
 // TARGET: audio = y (rows, n); writes the magnitudes and the tile's sum |Y|^2 (K = 1 partial).
 // else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row mr_target_of(cand) * C + ch;
 //         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).  A candidate whose slot names no target
 //         reads nothing from the table and writes no partial: k_mrstft_final gives it NaN.
 // SD:     C = 2 and audio = (items, 2, n) on both sides; row 2 item + 0 is the item's L + R, row 2 item + 1 its L - R.
 // MEL:    the table's rows are frames x n_bins band sums of the magnitudes, and both terms are taken between those.
-template <bool TARGET, bool SD, bool MEL>
-__global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDevOf<MEL> d, const float *__restrict__ audio, const float *__restrict__ peaks,
+// PRE:    the rows are filtered with d.taps in the loader (mr_prefiltered_span) before anything else sees them.
+template <bool TARGET, bool SD, bool MEL, bool PRE = false>
+__global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrArgOf<MEL, PRE> d, const float *__restrict__ audio, const float *__restrict__ peaks,
                                                       int norm_passes, int C, int per_target, const int32_t *__restrict__ slots,
                                                       int n_targets) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -301,15 +423,19 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrDevOf<MEL> d, const flo
     // the span: padded samples [t0 hop, t0 hop + (nf - 1) hop + N), padded index i = sample i - N / 2, reflected (no edge repeat)
     const int span_len = (nf - 1) * d.hop + N;
     const int64_t s0 = t0 * d.hop - N2;
-    for (int i = tid; i < span_len; i += MR_THREADS) {
-        int64_t s = s0 + i;
-        if (s < 0) s = -s;
-        if (s >= d.n) s = 2 * (d.n - 1) - s;
-        if (SD) {
-            const float l = x[s] * r1, r = x[d.n + s] * r1;
-            span[i] = (row & 1) ? l - r : l + r;
-        } else {
-            span[i] = x[s] * r1;
+    if constexpr (PRE) {
+        mr_prefiltered_span<SD>(x, d.n, r1, row, d.taps, d.n_taps, span, s0, span_len, tid);
+    } else {
+        for (int i = tid; i < span_len; i += MR_THREADS) {
+            int64_t s = s0 + i;
+            if (s < 0) s = -s;
+            if (s >= d.n) s = 2 * (d.n - 1) - s;
+            if (SD) {
+                const float l = x[s] * r1, r = x[d.n + s] * r1;
+                span[i] = (row & 1) ? l - r : l + r;
+            } else {
+                span[i] = x[s] * r1;
+            }
         }
     }
     __syncthreads();
@@ -475,6 +601,21 @@ static MrDevOf<MEL> mr_dev_of(const MrPlan &p, int i, int64_t n, float *table, d
     if constexpr (MEL) return mr_dev_mel(d, bank, i); else return d;
 }
 
+// ... and, for the prefiltered kernels, with the taps behind that.
+template <bool MEL, bool PRE>
+static MrArgOf<MEL, PRE> mr_arg_of(const MrPlan &p, int i, int64_t n, float *table, double *partial, int K, const stito_mel_bank *bank,
+                                   const float *taps_dev, int n_taps) {
+    const MrDevOf<MEL> d = mr_dev_of<MEL>(p, i, n, table, partial, K, bank);
+    if constexpr (PRE) {
+        MrDevPre<MrDevOf<MEL>> a;
+        static_cast<MrDevOf<MEL> &>(a) = d;
+        a.taps = taps_dev; a.n_taps = n_taps;
+        return a;
+    } else {
+        return d;
+    }
+}
+
 static MrSum mr_sum(const MrPlan &p) {
     MrSum s;
     s.n_res = p.n_res; s.tiles_total = p.tiles_total;
@@ -511,12 +652,13 @@ static int mr_sd_channels(const char *who, int channels) {
 
 // The one launch path of the table.  SD: y_dev is (rows / 2, 2, n) and row 2 t + 0 / 1 of the table is target t's L + R / L - R.
 // MEL: the rows of the table are band sums through `bank`, which has been checked.
-template <bool SD, bool MEL = false>
+// PRE: the rows are filtered with the n_taps taps at taps_dev, which have been checked.
+template <bool SD, bool MEL = false, bool PRE = false>
 static int mr_target(const char *who, const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
-                     void *stream, const stito_mel_bank *bank = nullptr) {
+                     void *stream, const stito_mel_bank *bank = nullptr, const float *taps_dev = nullptr, int n_taps = 0) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
-    STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0));
+    STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0, PRE));
     STITO_TRY(mr_device_fits(p));
     STITO_REQUIRE(rows >= 1, STITO_E_INVALID, "%s: %d rows", who, rows);
     STITO_REQUIRE(y_dev != nullptr && table_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);
@@ -525,11 +667,11 @@ static int mr_target(const char *who, const int *res, int n_res, const float *y_
     double *partial = sums + (int64_t)rows * p.n_res;
     for (int i = 0; i < p.n_res; ++i) {
         STITO_REQUIRE((int64_t)rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "%s: too many tiles", who);
-        const MrDevOf<MEL> d = mr_dev_of<MEL>(p, i, n_samples, table_dev, partial, 1, bank);
+        const MrArgOf<MEL, PRE> d = mr_arg_of<MEL, PRE>(p, i, n_samples, table_dev, partial, 1, bank, taps_dev, n_taps);
         hipLaunchKernelGGL(k_mrstft_tables, dim3((d.N + 255) / 256), dim3(256), 0, st, (float2 *)d.tw, (float *)d.win, d.N, p.win[i]);
         STITO_LAUNCH_CHECK();
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true, SD, MEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
-        hipLaunchKernelGGL((k_mrstft<true, SD, MEL>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<true, SD, MEL, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL((k_mrstft<true, SD, MEL, PRE>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, y_dev,
                            (const float *)nullptr, 0, 1, 1, (const int32_t *)nullptr, rows);
         STITO_LAUNCH_CHECK();
     }
@@ -553,14 +695,14 @@ extern "C" int stito_mrstft_target_sd(const int *res, int n_res, const float *y_
 
 // The one launch path of the loss: populations of pop / n_slots candidates, population k against target target_slot[k] of the
 // table's n_targets, or against target k when there is no slot list (then n_slots == n_targets).
-template <bool SD, bool MEL = false>
+template <bool SD, bool MEL = false, bool PRE = false>
 static int mr_loss(const char *who, const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                    const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
                    int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
-                   const stito_mel_bank *bank = nullptr) {
+                   const stito_mel_bank *bank = nullptr, const float *taps_dev = nullptr, int n_taps = 0) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
-    STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0));
+    STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0, PRE));
     STITO_TRY(mr_device_fits(p));
     STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "%s: pop %d, n_targets %d", who, pop, n_targets);
     STITO_REQUIRE(n_slots >= 1, STITO_E_INVALID, "%s: %d target slots", who, n_slots);
@@ -581,9 +723,9 @@ static int mr_loss(const char *who, const int *res, int n_res, const float *audi
     double *partial = (double *)workspace_dev;
     const double *ysum = (const double *)(table_dev + p.mags_base + trows * p.row_floats);
     for (int i = 0; i < p.n_res; ++i) {
-        const MrDevOf<MEL> d = mr_dev_of<MEL>(p, i, n_samples, (float *)table_dev, partial, 2, bank);
-        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false, SD, MEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
-        hipLaunchKernelGGL((k_mrstft<false, SD, MEL>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev,
+        const MrArgOf<MEL, PRE> d = mr_arg_of<MEL, PRE>(p, i, n_samples, (float *)table_dev, partial, 2, bank, taps_dev, n_taps);
+        STITO_HIP_CHECK(hipFuncSetAttribute((const void *)k_mrstft<false, SD, MEL, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]));
+        hipLaunchKernelGGL((k_mrstft<false, SD, MEL, PRE>), dim3((unsigned)(rows * p.tiles[i])), dim3(MR_THREADS), p.lds[i], st, d, audio_dev,
                            peaks_dev, norm_passes, channels, pop / n_slots, target_slot_dev, n_targets);
         STITO_LAUNCH_CHECK();
     }
@@ -656,4 +798,86 @@ extern "C" int stito_mrstft_loss_slots_mel(const int *res, int n_res, const stit
     STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots_mel: null target_slot_dev");
     return mr_loss<false, true>("stito_mrstft_loss_slots_mel", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
                                 target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank);
+}
+
+// The prefiltered variants (ABI 10.9): one trio for the three kinds -- 0 the L/R distance, 1 sum / difference, 2 mel (with its bank)
+// -- of rows that the loader filters with n_taps taps.  The table does not record the taps: table and loss calls take the same.
+static int mr_pf_check(const char *who, int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res) {
+    STITO_REQUIRE(kind >= 0 && kind <= 2, STITO_E_INVALID, "%s: kind %d is none of 0 (L/R), 1 (sum / difference), 2 (mel)", who, kind);
+    STITO_REQUIRE(n_taps >= 1 && n_taps <= MR_PF_MAX_TAPS, STITO_E_INVALID, "%s: n_taps %d, 1 .. %d are supported", who, n_taps, MR_PF_MAX_TAPS);
+    STITO_REQUIRE((n_taps & 1) == 1, STITO_E_INVALID, "%s: n_taps %d must be odd (the filter is centred on tap n_taps / 2)", who, n_taps);
+    STITO_REQUIRE(taps_dev != nullptr, STITO_E_INVALID, "%s: null taps_dev", who);
+    if (kind == 2) return mr_bank_check(who, bank, res, n_res);
+    STITO_REQUIRE(bank == nullptr, STITO_E_INVALID, "%s: kind %d takes no bank", who, kind);
+    return STITO_OK;
+}
+
+static bool mr_pf_sizes_ok(int kind, int n_bins, int n_taps) {
+    if (kind < 0 || kind > 2 || n_taps < 1 || n_taps > MR_PF_MAX_TAPS || (n_taps & 1) == 0) return false;
+    return kind == 2 ? (n_bins >= 1 && n_bins <= 256) : n_bins == 0;
+}
+
+extern "C" int64_t stito_mrstft_table_floats_pf(int kind, int n_bins, int n_taps, const int *res, int n_res, int rows, int64_t n_samples) {
+    MrPlan p;
+    if (!mr_pf_sizes_ok(kind, n_bins, n_taps) || rows < 1 || (kind == 1 && (rows & 1))) return 0;
+    if (mr_plan(res, n_res, n_samples, p, n_bins, true) != STITO_OK) return 0;
+    return mr_table_floats(p, rows);
+}
+
+extern "C" size_t stito_mrstft_workspace_bytes_pf(int kind, int n_taps, const int *res, int n_res, int pop, int channels, int64_t n_samples) {
+    MrPlan p;
+    if (!mr_pf_sizes_ok(kind, kind == 2 ? 1 : 0, n_taps) || pop < 1 || channels < 1 || channels > MR_MAX_CH || (kind == 1 && channels != 2))
+        return 0;
+    if (mr_plan(res, n_res, n_samples, p, 0, true) != STITO_OK || n_res * channels > 64) return 0;
+    return (size_t)pop * channels * p.tiles_total * 2 * sizeof(double);
+}
+
+extern "C" int stito_mrstft_target_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                                      const float *y_dev, int n_targets, int channels, int64_t n_samples, float *table_dev, void *stream) {
+    const char *who = "stito_mrstft_target_pf";
+    STITO_TRY(mr_pf_check(who, kind, bank, taps_dev, n_taps, res, n_res));
+    if (kind == 1) STITO_TRY(mr_sd_channels(who, channels));
+    STITO_REQUIRE(n_targets >= 1 && channels >= 1 && (int64_t)n_targets * channels < (1 << 30), STITO_E_INVALID, "%s: %d targets of %d channels",
+                  who, n_targets, channels);
+    const int rows = n_targets * channels;
+    if (kind == 1) return mr_target<true, false, true>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, nullptr, taps_dev, n_taps);
+    if (kind == 2) return mr_target<false, true, true>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, bank, taps_dev, n_taps);
+    return mr_target<false, false, true>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, nullptr, taps_dev, n_taps);
+}
+
+static int mr_loss_pf(const char *who, int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                      const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
+                      const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples, float *loss_dev,
+                      void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (kind == 1)
+        return mr_loss<true, false, true>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots, pop,
+                                          channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, nullptr, taps_dev, n_taps);
+    if (kind == 2)
+        return mr_loss<false, true, true>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots, pop,
+                                          channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank, taps_dev, n_taps);
+    return mr_loss<false, false, true>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots, pop,
+                                       channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, nullptr, taps_dev, n_taps);
+}
+
+extern "C" int stito_mrstft_loss_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                                    const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
+                                    int pop, int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
+                                    void *stream) {
+    const char *who = "stito_mrstft_loss_pf";
+    STITO_TRY(mr_pf_check(who, kind, bank, taps_dev, n_taps, res, n_res));
+    if (kind == 1) STITO_TRY(mr_sd_channels(who, channels));
+    return mr_loss_pf(who, kind, bank, taps_dev, n_taps, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets,
+                      pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int stito_mrstft_loss_slots_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
+                                          const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev,
+                                          int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
+                                          int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    const char *who = "stito_mrstft_loss_slots_pf";
+    STITO_TRY(mr_pf_check(who, kind, bank, taps_dev, n_taps, res, n_res));
+    if (kind == 1) STITO_TRY(mr_sd_channels(who, channels));
+    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "%s: null target_slot_dev", who);
+    return mr_loss_pf(who, kind, bank, taps_dev, n_taps, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev,
+                      n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }

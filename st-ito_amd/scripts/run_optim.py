@@ -26,7 +26,7 @@ from st_ito.style_transfer import process_audio, run_es, run_staged_es  # noqa: 
 from st_ito.utils import get_param_embeds, load_param_model, make_synthetic_param_model  # noqa: E402
 
 
-AUDIO_OBJECTIVES = ("mrstft", "mrstft-sd", "mrstft-mel")  # --objective values that are run_es's `distance` as they stand
+AUDIO_OBJECTIVES = ("mrstft", "mrstft-sd", "mrstft-mel", "mrstft-aw", "mrstft-sd-aw", "mrstft-mel-aw")  # --objective values that are run_es's `distance` as they stand
 
 
 def build_parser():
@@ -54,12 +54,14 @@ def build_parser():
     parser.add_argument("--no-early-stop", action="store_true")
     parser.add_argument("--no-find-w0", action="store_true")
     parser.add_argument("--output-dir", type=str, default="output/optim")
-    parser.add_argument("--objective", type=str, default="embedding", choices=["embedding", "mrstft", "mrstft-sd", "mrstft-mel"],
+    parser.add_argument("--objective", type=str, default="embedding", choices=["embedding", *AUDIO_OBJECTIVES],
                         help="embedding: cosine distance of the --metric embeddings (the reference); mrstft: multi-resolution STFT "
                              "distance to the target audio itself (same length as the input; no checkpoint is loaded); mrstft-sd: "
                              "that distance between the sums and differences of the two channels (a chain that renders stereo); mrstft-mel: "
                              "that distance between 64 mel-band sums of the magnitudes, so the near-silent bins above a few kHz no "
-                             "longer carry it")
+                             "longer carry it; mrstft-aw, mrstft-sd-aw, mrstft-mel-aw: those three after render and target went "
+                             "through the 101-tap A-weighting FIR of the sample rate (auraloss's perceptual_weighting), so what "
+                             "nobody hears no longer carries the distance")
     parser.add_argument("--device-es", action="store_true",
                         help="step the CMA-ES on the GPU (run_es(device_es=True)): same update rule, its own random stream; single "
                              "rank, no --savepop, not with --staged")

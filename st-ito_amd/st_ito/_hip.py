@@ -150,6 +150,16 @@ SIGNATURES = {
                                       c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "stito_mrstft_loss_slots_mel": (c_int, [POINTER(c_int), c_int, POINTER(MelBank), c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                             c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the prefiltered variants (ABI 10.9): (kind, bank or None, taps_dev, n_taps) before the unfiltered calls' arguments; the target
+    # call takes (n_targets, channels) like the _sd one; table and workspace have their own size functions
+    "stito_mrstft_table_floats_pf": (c_int64, [c_int, c_int, c_int, POINTER(c_int), c_int, c_int, c_int64]),
+    "stito_mrstft_workspace_bytes_pf": (c_size_t, [c_int, c_int, POINTER(c_int), c_int, c_int, c_int, c_int64]),
+    "stito_mrstft_target_pf": (c_int, [c_int, POINTER(MelBank), c_void_p, c_int, POINTER(c_int), c_int, c_void_p, c_int, c_int, c_int64,
+                                       c_void_p, c_void_p]),
+    "stito_mrstft_loss_pf": (c_int, [c_int, POINTER(MelBank), c_void_p, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "stito_mrstft_loss_slots_pf": (c_int, [c_int, POINTER(MelBank), c_void_p, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "stito_spectral_centroid_workspace_bytes": (c_size_t, [c_int, c_int, c_int64]),
     "stito_spectral_centroid": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

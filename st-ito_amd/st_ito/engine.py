@@ -800,3 +800,35 @@ class MelMrstftEvaluator(MrstftEvaluator):
         from . import features as _features
 
         return _features.MelMrstftTarget(y, resolutions=self.resolutions, bank=self._bank)
+
+
+class PrefilteredMrstftEvaluator(MrstftEvaluator):
+    """MrstftEvaluator with a distance on prefiltered rows (features.PrefilteredMrstftTarget; with prefilter="aw", auraloss's
+    perceptual_weighting=True at the evaluator's sample rate): render and target go through the FIR in the loss kernel's loader,
+    after the folded peak normalisation (and after the sums and differences under kind "sum-diff"), before the STFT.  kind: "lr",
+    "sum-diff" (the chain must render 2 channels) or "mel" (n_bins bands of the Slaney bank of the sample rate).  prefilter:
+    features.mrstft_prefilter's argument.  Taps and bank are built and checked on the host, before the base class touches the
+    device; the taps are uploaded once and stay on the device for the evaluator's lifetime, shared by all its tables.  Tables and
+    workspace are sized by the prefiltered calls' own size functions.  Everything else is the base class's."""
+
+    def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor,
+                 device: Optional[torch.device] = None, resolutions=None, normalize_stages: bool = False, kind: str = "lr",
+                 prefilter="aw", n_bins: int = 64):
+        from . import features as _features
+
+        if kind not in _features._PREFILTER_KINDS:
+            raise ValueError(f"kind must be one of {sorted(_features._PREFILTER_KINDS)}, got {kind!r}")
+        self.kind = kind
+        self.taps = _features.mrstft_prefilter(prefilter, sample_rate)
+        self._bank = _features.mel_mrstft_bank(sample_rate, n_bins, resolutions) if kind == "mel" else None
+        self._taps_dev = None
+        super().__init__(x, sample_rate, plugins, target_audio, device, resolutions, normalize_stages,
+                         "sum-diff" if kind == "sum-diff" else "lr")
+
+    def _target_table(self, y: torch.Tensor):
+        from . import features as _features
+
+        if self._taps_dev is None:
+            self._taps_dev = torch.from_numpy(self.taps).to(self.device)
+        return _features.PrefilteredMrstftTarget(y, self.taps, kind=self.kind, resolutions=self.resolutions, bank=self._bank,
+                                                 taps_dev=self._taps_dev)

@@ -306,10 +306,13 @@ class MrstftTarget:
         self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
         self.update(y)
 
-    # The three places where the kinds of table differ (MelMrstftTarget overrides them): the table's size, the call that fills
-    # it, and the two loss entry points with what they take between n_res and the audio.
+    # The places where the kinds of table differ (MelMrstftTarget and PrefilteredMrstftTarget override them): the table's size, the
+    # call that fills it, the two loss entry points with what they take between n_res and the audio, and the workspace's size.
     def _table_floats(self) -> int:
         return _hip.lib().stito_mrstft_table_floats(self.res, self.n_res, self.n_targets * self.channels, self.n)
+
+    def _workspace_bytes(self, pop: int) -> int:
+        return _hip.lib().stito_mrstft_workspace_bytes(self.res, self.n_res, pop, self.channels, self.n)
 
     def _fill(self, y: torch.Tensor) -> None:
         L = _hip.lib()
@@ -347,7 +350,7 @@ class MrstftTarget:
         audio = audio.contiguous()
         P = audio.shape[0]
         L = _hip.lib()
-        ws = _hip.scratch(L.stito_mrstft_workspace_bytes(self.res, self.n_res, P, self.channels, self.n), audio.device, ws, "mrstft")
+        ws = _hip.scratch(self._workspace_bytes(P), audio.device, ws, "mrstft")
         out = torch.empty(P, dtype=torch.float32, device=audio.device)
         plain, with_slots, between = self._loss_calls()
         if slots is None:
@@ -506,3 +509,141 @@ def compute_mel_mrstft_distance(x: torch.Tensor, y: torch.Tensor, sample_rate, n
     xin, dev = _gpu(x)
     yin = y.detach().to(dev, torch.float32).contiguous()
     return MelMrstftTarget(yin, resolutions=resolutions, bank=bank).loss(xin).to(x.device)
+
+
+# --------------------------------------------------------------------------------------------
+# the prefiltered forms (csrc/mrstft.hip's PRE variants): an FIR in the kernel's loader
+# --------------------------------------------------------------------------------------------
+MRSTFT_PREFILTER_MAX_TAPS = 255
+_PREFILTER_KINDS = {"lr": 0, "sum-diff": 1, "mel": 2}
+
+
+def _a_weighting_fir(sample_rate, n_taps: int = 101) -> np.ndarray:
+    """The "aw" design, float64: the analogue A-weighting prototype (corner frequencies 20.598997, 107.65265, 737.86223 and
+    12194.217 Hz, +1.9997 dB at 1 kHz) through the bilinear transform, its magnitude response on 512 frequencies, and a
+    frequency-sampling FIR of n_taps taps fitted to that magnitude."""
+    from scipy import signal
+
+    f1, f2, f3, f4 = 20.598997, 107.65265, 737.86223, 12194.217
+    num = [(2 * np.pi * f4) ** 2 * 10 ** (1.9997 / 20), 0.0, 0.0, 0.0, 0.0]
+    den = np.polymul([1.0, 4 * np.pi * f4, (2 * np.pi * f4) ** 2], [1.0, 4 * np.pi * f1, (2 * np.pi * f1) ** 2])
+    den = np.polymul(np.polymul(den, [1.0, 2 * np.pi * f3]), [1.0, 2 * np.pi * f2])
+    b, a = signal.bilinear(num, den, fs=float(sample_rate))
+    w, h = signal.freqz(b, a, worN=512, fs=float(sample_rate), include_nyquist=True)
+    return signal.firwin2(n_taps, w, np.abs(h), fs=float(sample_rate))
+
+
+def mrstft_prefilter(spec, sample_rate=None) -> np.ndarray:
+    """The taps of a prefilter of the MR-STFT distances, float32, built and checked on the host (no GPU needed).  spec: "aw" --
+    the 101-tap A-weighting FIR of auraloss's perceptual_weighting=True at `sample_rate` (restated, unpinned: auraloss is not
+    installed here), designed in float64 and rounded once -- or a 1-D array of taps, used as they are.  The filter is applied as
+    torch.nn.functional.conv1d(x, taps, padding=len(taps) // 2): cross-correlation, zero padding, same length.
+
+    The "aw" recipe evaluates the response with scipy.signal.freqz(..., include_nyquist=True): this project's choice, because
+    scipy.signal.firwin2 wants the frequency grid to end at sample_rate / 2 and raises without it.  101 taps cannot reach
+    A-weighting's -19 dB at 100 Hz (-8.5 dB at 48 kHz): a property of that filter, not a defect of this one.
+
+    ValueError for an even or empty length, more than 255 taps, non-finite values, an unknown name, or "aw" without a rate."""
+    if isinstance(spec, str):
+        if spec != "aw":
+            raise ValueError(f"unknown prefilter {spec!r}: 'aw' or a 1-D array of taps")
+        if sample_rate is None or not float(sample_rate) > 0:
+            raise ValueError(f"prefilter 'aw' is designed for a sample rate: sample_rate is {sample_rate!r}")
+        taps = _a_weighting_fir(sample_rate)
+    else:
+        taps = np.asarray(spec.detach().cpu() if isinstance(spec, torch.Tensor) else spec, dtype=np.float64)
+        if taps.ndim != 1:
+            raise ValueError(f"prefilter taps must be 1-D, got shape {taps.shape}")
+    if taps.size < 1 or taps.size % 2 == 0:
+        raise ValueError(f"a prefilter has an odd number of taps (it is centred on tap len // 2), got {taps.size}")
+    if taps.size > MRSTFT_PREFILTER_MAX_TAPS:
+        raise ValueError(f"a prefilter has at most {MRSTFT_PREFILTER_MAX_TAPS} taps, got {taps.size}")
+    if not np.all(np.isfinite(taps)):
+        raise ValueError("prefilter taps must be finite")
+    return np.ascontiguousarray(taps.astype(np.float32))
+
+
+class PrefilteredMrstftTarget(MrstftTarget):
+    """MrstftTarget for a distance on prefiltered rows (auraloss's perceptual_weighting=True with prefilter="aw"; restated,
+    unpinned): target and candidates go through the FIR `prefilter` (mrstft_prefilter's argument; "aw" needs sample_rate) after
+    the peak normalisation and, under kind "sum-diff", after [L + R, L - R] are formed, and before the STFT, whose reflect padding
+    reflects the filtered row.  The filter runs in the fused kernel's loader (stito_mrstft_loss_pf): no filtered copy of the
+    population is written.  kind: "lr" (compute_mrstft_distance's), "sum-diff" (compute_sd_mrstft_distance's; 2 channels) or "mel"
+    (compute_mel_mrstft_distance's: sample_rate and n_bins, or `bank`, as MelMrstftTarget takes them).  The taps are uploaded once
+    and live as long as the object; taps_dev: a device tensor that already holds exactly these taps (an evaluator's)."""
+
+    def __init__(self, y: torch.Tensor, prefilter, sample_rate=None, kind: str = "lr", n_bins: int = MEL_MRSTFT_BINS, resolutions=None,
+                 bank=None, taps_dev=None):
+        if kind not in _PREFILTER_KINDS:
+            raise ValueError(f"kind must be one of {sorted(_PREFILTER_KINDS)}, got {kind!r}")
+        self.kind = kind
+        self.taps = mrstft_prefilter(prefilter, sample_rate)
+        self._host_bank = self._bank = None
+        self.n_bins = 0
+        if kind == "mel":
+            if bank is None:
+                if sample_rate is None:
+                    raise ValueError("kind 'mel' needs a sample_rate (or a bank)")
+                bank = mel_mrstft_bank(sample_rate, n_bins, resolutions)
+            self._host_bank, self.n_bins = bank, len(bank[0][0])
+        elif bank is not None:
+            raise ValueError(f"kind {kind!r} takes no bank")
+        self._taps_dev = taps_dev
+        super().__init__(y, resolutions, "sum-diff" if kind == "sum-diff" else "lr")
+
+    def _head(self):
+        """(kind, bank or None, taps_dev, n_taps): what every prefiltered call takes first."""
+        dev = self.table.device
+        if self._taps_dev is None:
+            self._taps_dev = torch.from_numpy(self.taps).to(dev)
+        assert self._taps_dev.is_cuda and self._taps_dev.dtype == torch.float32 and self._taps_dev.numel() == self.taps.size
+        bank = None
+        if self.kind == "mel":
+            if self._bank is None:
+                self._bank = _DeviceMelBank(self._host_bank, dev)
+            bank = self._bank.ref
+        return _PREFILTER_KINDS[self.kind], bank, _hip.ptr(self._taps_dev), int(self.taps.size)
+
+    def _table_floats(self) -> int:
+        return _hip.lib().stito_mrstft_table_floats_pf(_PREFILTER_KINDS[self.kind], self.n_bins, int(self.taps.size), self.res, self.n_res,
+                                                       self.n_targets * self.channels, self.n)
+
+    def _workspace_bytes(self, pop: int) -> int:
+        return _hip.lib().stito_mrstft_workspace_bytes_pf(_PREFILTER_KINDS[self.kind], int(self.taps.size), self.res, self.n_res, pop,
+                                                          self.channels, self.n)
+
+    def _fill(self, y: torch.Tensor) -> None:
+        _hip.check(_hip.lib().stito_mrstft_target_pf(*self._head(), self.res, self.n_res, _hip.ptr(y), self.n_targets, self.channels,
+                                                     self.n, _hip.ptr(self.table), _hip.stream_ptr()))
+
+    def _loss_calls(self):
+        import functools
+
+        L, head = _hip.lib(), self._head()
+        return functools.partial(L.stito_mrstft_loss_pf, *head), functools.partial(L.stito_mrstft_loss_slots_pf, *head), ()
+
+
+def compute_prefiltered_mrstft_distance(x: torch.Tensor, y: torch.Tensor, prefilter, sample_rate=None, kind: str = "lr",
+                                        n_bins: int = MEL_MRSTFT_BINS, resolutions=None) -> torch.Tensor:
+    """compute_mrstft_distance (kind "lr"), compute_sd_mrstft_distance ("sum-diff") or compute_mel_mrstft_distance ("mel") of
+    estimate and reference after both went through the FIR `prefilter` -- with "aw", auraloss's perceptual_weighting=True
+    (restated, unpinned) -> (B,) float32 on x's device.  Same shape rules as those; sample_rate is needed for "aw" and for "mel".
+    Every ValueError -- the taps, the kind, an empty mel band, the shapes -- comes before anything touches the GPU."""
+    if kind not in _PREFILTER_KINDS:
+        raise ValueError(f"kind must be one of {sorted(_PREFILTER_KINDS)}, got {kind!r}")
+    taps = mrstft_prefilter(prefilter, sample_rate)
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("expected (bs, chs, seq_len)")
+    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _mrstft_stereo("sum-diff" if kind == "sum-diff" else "lr", x.shape[1])
+    bank = None
+    if kind == "mel":
+        if sample_rate is None:
+            raise ValueError("kind 'mel' needs a sample_rate")
+        bank = mel_mrstft_bank(sample_rate, n_bins, resolutions)
+    _mrstft_res(resolutions)
+    _mrstft_check_length(x.shape[-1], resolutions)
+    xin, dev = _gpu(x)
+    yin = y.detach().to(dev, torch.float32).contiguous()
+    return PrefilteredMrstftTarget(yin, taps, kind=kind, resolutions=resolutions, bank=bank).loss(xin).to(x.device)

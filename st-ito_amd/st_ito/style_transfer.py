@@ -487,19 +487,25 @@ def _check_device_es(plugins, popsize, max_iters, savepop, sync_every):
 
 
 # the objectives that compare the rendered AUDIO with the target's: "mrstft" channel by channel, "mrstft-sd" on [L + R, L - R],
-# "mrstft-mel" channel by channel on mel-band sums of the magnitudes
-_AUDIO_DISTANCES = ("mrstft", "mrstft-sd", "mrstft-mel")
+# "mrstft-mel" channel by channel on mel-band sums of the magnitudes; "-aw": the same three on rows that went through the A-weighting
+# FIR of the sample rate first (auraloss's perceptual_weighting=True; engine.PrefilteredMrstftEvaluator)
+_PREFILTERED_DISTANCES = {"mrstft-aw": "lr", "mrstft-sd-aw": "sum-diff", "mrstft-mel-aw": "mel"}   # name -> the evaluator's kind
+_AUDIO_DISTANCES = ("mrstft", "mrstft-sd", "mrstft-mel") + tuple(_PREFILTERED_DISTANCES)
 
 
 def _check_distance(distance, sample_rate=None):
-    """The name -- and, under "mrstft-mel", the bank of the sample rate, built on the host: a band with no bin is a ValueError
-    here, before an input is normalised or anything launched."""
+    """The name -- and, under "mrstft-mel" and "mrstft-mel-aw", the bank of the sample rate, built on the host: a band with no bin
+    is a ValueError here, before an input is normalised or anything launched; so are the "-aw" taps of that rate."""
     if distance != "cosine" and distance not in _AUDIO_DISTANCES:
         raise ValueError(f"Unknown distance: {distance}")
-    if distance == "mrstft-mel":
+    if distance in ("mrstft-mel", "mrstft-mel-aw"):
         from . import features
 
         features.mel_mrstft_bank(sample_rate)
+    if distance in _PREFILTERED_DISTANCES:
+        from . import features
+
+        features.mrstft_prefilter("aw", sample_rate)
 
 
 def _check_mrstft_pairs(input_audios, target_audios, plugins, target="target {b}", chain="the chain", distance="mrstft"):
@@ -515,8 +521,8 @@ def _check_mrstft_pairs(input_audios, target_audios, plugins, target="target {b}
             raise ValueError(f"distance '{distance}' compares sample spans: {who} {tuple(t.shape)} must have the length of its input "
                              f"{tuple(x.shape)}")
         c_out = engine.chain_out_channels(plugins, x.shape[0])
-        if distance == "mrstft-sd" and c_out != 2:
-            raise ValueError(f"distance 'mrstft-sd' compares the sums and differences of 2 channels: {chain} renders {c_out} channels "
+        if distance in ("mrstft-sd", "mrstft-sd-aw") and c_out != 2:
+            raise ValueError(f"distance '{distance}' compares the sums and differences of 2 channels: {chain} renders {c_out} channels "
                              f"from input {b}'s {x.shape[0]}")
         if t.shape[0] != c_out:
             raise ValueError(f"distance '{distance}': {who} has {t.shape[0]} channels, {chain} renders {c_out}")
@@ -530,13 +536,15 @@ def _check_mrstft_savepop(savepop, distance="mrstft"):
 def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
     """The one place that turns `distance` into an evaluator, both resolved through `engine` when called.  target: the target
     embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft",
-    "mrstft-sd" and "mrstft-mel", which embed nothing and launch eagerly: kw has nothing to say to them)."""
+    "mrstft-sd", "mrstft-mel" and their "-aw" forms, which embed nothing and launch eagerly: kw has nothing to say to them)."""
     if distance == "mrstft":
         return engine.MrstftEvaluator(x, sample_rate, plugins, target)
     if distance == "mrstft-sd":
         return engine.MrstftEvaluator(x, sample_rate, plugins, target, stereo="sum-diff")
     if distance == "mrstft-mel":
         return engine.MelMrstftEvaluator(x, sample_rate, plugins, target)
+    if distance in _PREFILTERED_DISTANCES:
+        return engine.PrefilteredMrstftEvaluator(x, sample_rate, plugins, target, kind=_PREFILTERED_DISTANCES[distance], prefilter="aw")
     return engine.PopulationEvaluator(x, sample_rate, plugins, model, target, **kw)
 
 
@@ -686,7 +694,8 @@ def run_staged_es(
     (model and embed_func may be None, nothing is embedded); everything else is as above.  Every stage's sub-chain must
     render the target's channel count, and savepop is refused as run_es refuses it for this objective.  distance="mrstft-sd"
     is the same with the sum / difference distance: every stage's sub-chain must render 2 channels; distance="mrstft-mel" is
-    distance="mrstft" on mel-band sums of the magnitudes (engine.MelMrstftEvaluator)."""
+    distance="mrstft" on mel-band sums of the magnitudes (engine.MelMrstftEvaluator).  "mrstft-aw", "mrstft-sd-aw" and "mrstft-mel-aw"
+    are those three on rows that went through the A-weighting FIR of the sample rate first (engine.PrefilteredMrstftEvaluator)."""
     _check_distance(distance, sample_rate)
     savepop = bool(savepop or save_pop)
     names = list(plugins.keys())
@@ -808,7 +817,11 @@ def run_es_batch(
     and differences of the two channels (MrstftEvaluator(stereo="sum-diff")); the chain must render exactly 2 channels.
 
     distance="mrstft-mel": the same again with the distance taken between 64 mel-band sums of the magnitudes
-    (engine.MelMrstftEvaluator), channels compared L/R; any channel count the chain renders."""
+    (engine.MelMrstftEvaluator), channels compared L/R; any channel count the chain renders.
+
+    distance="mrstft-aw", "mrstft-sd-aw", "mrstft-mel-aw": the three above with render and target A-weighted first -- auraloss's
+    perceptual_weighting=True, the 101-tap FIR of features.mrstft_prefilter("aw", sample_rate), applied in the loss kernel's loader
+    (engine.PrefilteredMrstftEvaluator); the 2-channel rule and the empty-band rule of their plain forms hold."""
     _check_distance(distance, sample_rate)
     ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
     if ragged:
