@@ -114,7 +114,8 @@ int stito_version(void);
  * 7 = stito_mrstft_target_sd, stito_mrstft_loss_sd, stito_mrstft_loss_slots_sd; 8 = stito_mel_bank, stito_mrstft_table_floats_mel,
  * stito_mrstft_target_mel, stito_mrstft_loss_mel, stito_mrstft_loss_slots_mel; 9 = the prefiltered MR-STFT distances,
  * stito_mrstft_table_floats_pf, stito_mrstft_workspace_bytes_pf, stito_mrstft_target_pf, stito_mrstft_loss_pf,
- * stito_mrstft_loss_slots_pf. */
+ * stito_mrstft_loss_slots_pf; 10 = the waveform distances, stito_waveform_tile_samples, stito_waveform_table_floats,
+ * stito_waveform_workspace_bytes, stito_waveform_target, stito_waveform_loss, stito_waveform_loss_slots. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -651,6 +652,42 @@ int stito_mrstft_loss_slots_pf(int kind, const stito_mel_bank *bank, const float
                                const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
                                const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples, float *loss_dev,
                                void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* ---- waveform distances as objectives (ABI 10.10; csrc/waveform.hip) ----------------------------------------------------------- */
+/* The time-domain yardsticks auraloss.time ships beside the MR-STFT ones (ESRLoss, DCLoss, SNRLoss, SISDRLoss, LogCoshLoss;
+ * restated, PARITY UNPINNED), of a rendered population against target audio, in one pass over the rows.  A row is one channel of
+ * one item: x the candidate's after the peak normalisation of norm_passes (x * (1 / clip(peak, 1e-8)), as stito_mrstft_loss folds
+ * it), y the target's, n_samples float32 each.  With n_taps > 0 both first go through the FIR of the prefiltered MR-STFT calls,
+ * p[i] = sum_k taps[k] row[i + k - n_taps / 2] with zero padding (n_taps odd, <= 255; taps_dev on the device); n_taps 0: p = row and
+ * taps_dev is not read.  d = p_x - p_y, eps = 1e-8, and per row, `kind` being
+ *     0 esr      sum d^2 / (sum p_y^2 + eps)
+ *     1 dc       (sum d / n)^2 / (sum p_y^2 / n + eps)
+ *     2 snr      -10 log10(sum p_y^2 / (sum d^2 + eps) + eps)
+ *     3 sisdr    -10 log10(sum t^2 / (sum res^2 + eps) + eps): x', y' the rows minus their means, t = alpha y',
+ *                alpha = sum x' y' / (sum y'^2 + eps), res = x' - t
+ *     4 logcosh  (1 / n) sum ln(cosh d + eps), a sample with d == 0 adding exactly 0 (not ln(1 + eps) = 1e-8)
+ * a candidate's value is the mean over its rows.  The sums are taken in float64 in a fixed order (per lane, per tile, tiles in
+ * order), without atomics: a candidate's bits are the same at every position of every batch and under every slot list, a NaN stays
+ * in its candidate, and esr, dc and logcosh of y against its own table are exactly 0 (norm_passes 0).
+ * stito_waveform_target: y_dev (rows, n_samples) -> table_dev (stito_waveform_table_floats floats, 16-byte aligned): the filtered rows
+ * and their float64 sums; written by the kernel that filters the candidates.  The table does not record the taps: the loss call
+ * takes the same.  stito_waveform_loss_slots: audio_dev (pop, channels, n_samples), channels <= 8, against a table of n_targets *
+ * channels rows; target_slot_dev / n_slots as in stito_mrstft_loss_slots (NaN for a slot that names no target); workspace of
+ * stito_waveform_workspace_bytes bytes, 8-byte aligned.  stito_waveform_loss is that call with the identity map.
+ * stito_waveform_tile_samples: the samples of a tile (where the order of the sums changes shape), for tests to aim at.  The three
+ * size functions return 0 for arguments the launches refuse.  STITO_E_INVALID, naming the value, before any launch: kind outside
+ * 0 .. 4, n_taps even or outside [0, 255], null taps_dev with n_taps > 0, n_samples < 1, channels outside 1 .. 8. */
+int stito_waveform_tile_samples(int n_taps);
+int64_t stito_waveform_table_floats(int n_taps, int rows, int64_t n_samples);
+size_t stito_waveform_workspace_bytes(int n_taps, int pop, int channels, int64_t n_samples);
+int stito_waveform_target(const float *taps_dev, int n_taps, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
+                          void *stream);
+int stito_waveform_loss(int kind, const float *taps_dev, int n_taps, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                        const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
+                        void *workspace_dev, size_t workspace_bytes, void *stream);
+int stito_waveform_loss_slots(int kind, const float *taps_dev, int n_taps, const float *audio_dev, const float *peaks_dev, int norm_passes,
+                              const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
+                              int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ---- embeddings -> fitness ----------------------------------------------------------------- */
 /* In place: NaN scrub (utils.py:491-497), L2-normalise mid/side (n_cand, E).  If target_mid_dev

@@ -26,7 +26,8 @@ from st_ito.style_transfer import process_audio, run_es, run_staged_es  # noqa: 
 from st_ito.utils import get_param_embeds, load_param_model, make_synthetic_param_model  # noqa: E402
 
 
-AUDIO_OBJECTIVES = ("mrstft", "mrstft-sd", "mrstft-mel", "mrstft-aw", "mrstft-sd-aw", "mrstft-mel-aw")  # --objective values that are run_es's `distance` as they stand
+AUDIO_OBJECTIVES = ("mrstft", "mrstft-sd", "mrstft-mel", "mrstft-aw", "mrstft-sd-aw", "mrstft-mel-aw",
+                    "esr", "snr", "sisdr", "logcosh", "esr-aw", "snr-aw", "sisdr-aw", "logcosh-aw")  # --objective values that are run_es's `distance` as they stand
 
 
 def build_parser():
@@ -61,7 +62,10 @@ def build_parser():
                              "that distance between 64 mel-band sums of the magnitudes, so the near-silent bins above a few kHz no "
                              "longer carry it; mrstft-aw, mrstft-sd-aw, mrstft-mel-aw: those three after render and target went "
                              "through the 101-tap A-weighting FIR of the sample rate (auraloss's perceptual_weighting), so what "
-                             "nobody hears no longer carries the distance")
+                             "nobody hears no longer carries the distance; esr, snr, sisdr, logcosh: waveform distances to the "
+                             "target audio, sample against sample (error-to-signal ratio, SNR, scale-invariant SDR, log-cosh), which "
+                             "see polarity and alignment and cost one pass over the render; esr-aw, snr-aw, sisdr-aw, logcosh-aw: "
+                             "those behind the same A-weighting FIR")
     parser.add_argument("--device-es", action="store_true",
                         help="step the CMA-ES on the GPU (run_es(device_es=True)): same update rule, its own random stream; single "
                              "rank, no --savepop, not with --staged")

@@ -160,7 +160,16 @@ SIGNATURES = {
                                      c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "stito_mrstft_loss_slots_pf": (c_int, [c_int, POINTER(MelBank), c_void_p, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_int,
                                            c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "stito_spectral_centroid_workspace_bytes": (c_size_t, [c_int, c_int, c_int64]),
+    # the waveform distances (ABI 10.10): (kind, taps_dev, n_taps) before stito_mrstft_loss(_slots)'s arguments from audio_dev on
+    "stito_waveform_tile_samples": (c_int, [c_int]),
+    "stito_waveform_table_floats": (c_int64, [c_int, c_int, c_int64]),
+    "stito_waveform_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64]),
+    "stito_waveform_target": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "stito_waveform_loss": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "stito_waveform_loss_slots": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                          c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "stito_spectral_centroid_workspace_bytes":(c_size_t, [c_int, c_int, c_int64]),
     "stito_spectral_centroid": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),
     "stito_embed_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -777,8 +777,10 @@ class MrstftEvaluator(_Evaluator):
         Wt = self._on_device(Wn)
         audio, peaks = render_population(self.plugins, x[0] if x.shape[0] == 1 else x, Wt, self.sample_rate, self.chain, ws=self.ws)
         self.rendered_candidates += Wn.shape[0]
-        loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots, ws=self.ws)
+        loss = tgt.loss(audio, peaks, norm_passes=1, slots=slots, ws=self.ws, **self._loss_options)
         return loss, {}, (normalize_audio_(audio, peaks) if want_audio else None)
+
+    _loss_options = {}  # what a subclass's tables take in `loss` beyond the above (WaveformEvaluator: its kind)
 
 
 class MelMrstftEvaluator(MrstftEvaluator):
@@ -832,3 +834,32 @@ class PrefilteredMrstftEvaluator(MrstftEvaluator):
             self._taps_dev = torch.from_numpy(self.taps).to(self.device)
         return _features.PrefilteredMrstftTarget(y, self.taps, kind=self.kind, resolutions=self.resolutions, bank=self._bank,
                                                  taps_dev=self._taps_dev)
+
+
+class WaveformEvaluator(MrstftEvaluator):
+    """MrstftEvaluator with a waveform distance as the objective (features.WaveformTarget, csrc/waveform.hip): kind "esr", "dc",
+    "snr", "sisdr" or "logcosh" of the render, after process_audio's peak normalisation folded into the kernel, against the target
+    audio -- sample against sample, so polarity, alignment and time of arrival count, which no magnitude-spectrogram distance
+    sees.  prefilter: None, or features.mrstft_prefilter's argument ("aw": the A-weighting FIR of the evaluator's sample rate) --
+    render and target go through it in the kernel.  Kind and taps are checked on the host, before the base class touches the
+    device; the taps are uploaded once and shared by all the evaluator's tables.  A table is the target's filtered rows and their
+    sums and serves every kind.  Everything else -- the length policy, static and refilled tables, pairs= / x= / y=, the slot list,
+    a device-resident W, the workspace -- is the base class's."""
+
+    def __init__(self, x: torch.Tensor, sample_rate: int, plugins: Dict[str, dict], target_audio: torch.Tensor, kind: str = "esr",
+                 prefilter=None, device: Optional[torch.device] = None, normalize_stages: bool = False):
+        from . import features as _features
+
+        _features._waveform_kind(kind)
+        self.kind = kind
+        self.taps = _features._waveform_taps(prefilter, sample_rate)
+        self._taps_dev = None
+        self._loss_options = {"kind": kind}
+        super().__init__(x, sample_rate, plugins, target_audio, device, None, normalize_stages)
+
+    def _target_table(self, y: torch.Tensor):
+        from . import features as _features
+
+        if self.taps is not None and self._taps_dev is None:
+            self._taps_dev = torch.from_numpy(self.taps).to(self.device)
+        return _features.WaveformTarget(y, self.taps, taps_dev=self._taps_dev)

@@ -647,3 +647,108 @@ def compute_prefiltered_mrstft_distance(x: torch.Tensor, y: torch.Tensor, prefil
     xin, dev = _gpu(x)
     yin = y.detach().to(dev, torch.float32).contiguous()
     return PrefilteredMrstftTarget(yin, taps, kind=kind, resolutions=resolutions, bank=bank).loss(xin).to(x.device)
+
+
+# --------------------------------------------------------------------------------------------
+# waveform distances (csrc/waveform.hip): ESR, DC, SNR, SI-SDR, log-cosh in one pass over the rows
+# --------------------------------------------------------------------------------------------
+WAVEFORM_KINDS = {"esr": 0, "dc": 1, "snr": 2, "sisdr": 3, "logcosh": 4}
+WAVEFORM_MAX_CHANNELS = 8
+
+
+def _waveform_kind(kind) -> int:
+    if kind not in WAVEFORM_KINDS:
+        raise ValueError(f"kind must be one of {sorted(WAVEFORM_KINDS)}, got {kind!r}")
+    return WAVEFORM_KINDS[kind]
+
+
+def _waveform_taps(prefilter, sample_rate):
+    """None for no prefilter, else mrstft_prefilter's float32 taps (same refusals)."""
+    return None if prefilter is None else mrstft_prefilter(prefilter, sample_rate)
+
+
+def _waveform_check_shape(channels: int, n: int) -> None:
+    if not 1 <= int(channels) <= WAVEFORM_MAX_CHANNELS:
+        raise ValueError(f"Invalid number of channels: {int(channels)}")
+    if int(n) < 1:
+        raise ValueError(f"{int(n)} samples: the waveform distances need at least 1")
+
+
+class WaveformTarget:
+    """The target side of the waveform distances on the device, the shape of MrstftTarget: the table stito_waveform_target writes for
+    y (T, C, n) -- the rows after the prefilter (a copy of y without one) and their float64 sums -- in a buffer that `update` refills
+    for another y of the same shape.  prefilter: None, or mrstft_prefilter's argument ("aw" needs sample_rate): target and
+    candidates go through that FIR after the peak normalisation, in the kernel (no filtered copy of the population is written).
+    One table serves every kind: `loss(..., kind=)` picks esr, dc, snr, sisdr or logcosh (auraloss.time's ESRLoss, DCLoss, SNRLoss,
+    SISDRLoss, LogCoshLoss, restated, parity unpinned; the formulas stand in include/stito_hip.h).  taps_dev: a device tensor that
+    already holds exactly these taps (an evaluator's)."""
+
+    def __init__(self, y: torch.Tensor, prefilter=None, sample_rate=None, taps_dev=None):
+        self.taps = _waveform_taps(prefilter, sample_rate)
+        self.n_taps = 0 if self.taps is None else int(self.taps.size)
+        if y.dim() != 3:
+            raise ValueError("expected (n_targets, chs, seq_len)")
+        _waveform_check_shape(y.shape[1], y.shape[2])
+        self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
+        self._taps_dev = taps_dev
+        floats = _hip.lib().stito_waveform_table_floats(self.n_taps, self.n_targets * self.channels, self.n)
+        if floats <= 0:
+            raise ValueError(f"no waveform table for {tuple(y.shape)} audio")
+        self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
+        self.update(y)
+
+    def _taps_ptr(self):
+        if self.taps is None:
+            return None
+        if self._taps_dev is None:
+            self._taps_dev = torch.from_numpy(self.taps).to(self.table.device)
+        assert self._taps_dev.is_cuda and self._taps_dev.dtype == torch.float32 and self._taps_dev.numel() == self.n_taps
+        return _hip.ptr(self._taps_dev)
+
+    def update(self, y: torch.Tensor) -> "WaveformTarget":
+        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
+        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
+            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
+        _hip.check(_hip.lib().stito_waveform_target(self._taps_ptr(), self.n_taps, _hip.ptr(y.contiguous()), self.n_targets * self.channels,
+                                                    self.n, _hip.ptr(self.table), _hip.stream_ptr()))
+        return self
+
+    def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None, ws=None, kind: str = "esr") -> torch.Tensor:
+        """audio (P, C, n) float32 on the GPU -> (P,) float32, candidate p against target p // (P // T); peaks / norm_passes / slots /
+        ws: as MrstftTarget.loss (the folded peak normalisation, the slot list of stito_waveform_loss_slots, the evaluator's
+        engine.Workspace).  kind: "esr", "dc", "snr", "sisdr" or "logcosh"."""
+        k = _waveform_kind(kind)
+        if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
+            raise ValueError(f"audio must be (P, {self.channels}, {self.n}), got {tuple(audio.shape)}")
+        assert audio.is_cuda and audio.dtype == torch.float32
+        audio = audio.contiguous()
+        P = audio.shape[0]
+        L = _hip.lib()
+        ws = _hip.scratch(L.stito_waveform_workspace_bytes(self.n_taps, P, self.channels, self.n), audio.device, ws, "waveform")
+        out = torch.empty(P, dtype=torch.float32, device=audio.device)
+        head = (k, self._taps_ptr(), self.n_taps, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table), self.n_targets)
+        tail = (P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr())
+        if slots is None:
+            _hip.check(L.stito_waveform_loss(*head, *tail))
+            return out
+        if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
+            raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
+        _hip.check(L.stito_waveform_loss_slots(*head, _hip.ptr(slots), slots.numel(), *tail))
+        return out
+
+
+def compute_waveform_distance(x: torch.Tensor, y: torch.Tensor, kind: str = "esr", prefilter=None, sample_rate=None) -> torch.Tensor:
+    """The waveform distance `kind` ("esr", "dc", "snr", "sisdr", "logcosh": auraloss.time's losses, restated, unpinned) of
+    estimate x (B, C, n) and reference y (B, C, n) or (1, C, n), per item -> (B,) float32 on x's device: the mean over the item's
+    channels.  prefilter: None, or mrstft_prefilter's argument -- both sides go through that FIR first (ESR behind a pre-emphasis
+    filter); "aw" needs sample_rate.  Every ValueError -- the kind, the taps, the shapes -- comes before anything touches the GPU."""
+    _waveform_kind(kind)
+    taps = _waveform_taps(prefilter, sample_rate)
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("expected (bs, chs, seq_len)")
+    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _waveform_check_shape(x.shape[1], x.shape[2])
+    xin, dev = _gpu(x)
+    yin = y.detach().to(dev, torch.float32).contiguous()
+    return WaveformTarget(yin, taps).loss(xin, kind=kind).to(x.device)

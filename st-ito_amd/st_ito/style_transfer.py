@@ -490,7 +490,11 @@ def _check_device_es(plugins, popsize, max_iters, savepop, sync_every):
 # "mrstft-mel" channel by channel on mel-band sums of the magnitudes; "-aw": the same three on rows that went through the A-weighting
 # FIR of the sample rate first (auraloss's perceptual_weighting=True; engine.PrefilteredMrstftEvaluator)
 _PREFILTERED_DISTANCES = {"mrstft-aw": "lr", "mrstft-sd-aw": "sum-diff", "mrstft-mel-aw": "mel"}   # name -> the evaluator's kind
-_AUDIO_DISTANCES = ("mrstft", "mrstft-sd", "mrstft-mel") + tuple(_PREFILTERED_DISTANCES)
+# the waveform distances (engine.WaveformEvaluator, csrc/waveform.hip): sample against sample, so polarity and alignment count;
+# name -> (the evaluator's kind, its prefilter).  "dc" is a kind of features.compute_waveform_distance only.
+_WAVEFORM_DISTANCES = {name + suffix: (name, prefilter) for suffix, prefilter in (("", None), ("-aw", "aw"))
+                       for name in ("esr", "snr", "sisdr", "logcosh")}
+_AUDIO_DISTANCES = ("mrstft", "mrstft-sd", "mrstft-mel") + tuple(_PREFILTERED_DISTANCES) + tuple(_WAVEFORM_DISTANCES)
 
 
 def _check_distance(distance, sample_rate=None):
@@ -502,7 +506,7 @@ def _check_distance(distance, sample_rate=None):
         from . import features
 
         features.mel_mrstft_bank(sample_rate)
-    if distance in _PREFILTERED_DISTANCES:
+    if distance in _PREFILTERED_DISTANCES or _WAVEFORM_DISTANCES.get(distance, (None, None))[1] == "aw":
         from . import features
 
         features.mrstft_prefilter("aw", sample_rate)
@@ -536,7 +540,8 @@ def _check_mrstft_savepop(savepop, distance="mrstft"):
 def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
     """The one place that turns `distance` into an evaluator, both resolved through `engine` when called.  target: the target
     embeddings ("cosine"; kw: PopulationEvaluator's embed_func, entry_weights, use_graph) or the target audio ("mrstft",
-    "mrstft-sd", "mrstft-mel" and their "-aw" forms, which embed nothing and launch eagerly: kw has nothing to say to them)."""
+    "mrstft-sd", "mrstft-mel" and their "-aw" forms, and the waveform distances "esr", "snr", "sisdr", "logcosh" with theirs, which
+    embed nothing and launch eagerly: kw has nothing to say to them)."""
     if distance == "mrstft":
         return engine.MrstftEvaluator(x, sample_rate, plugins, target)
     if distance == "mrstft-sd":
@@ -545,6 +550,9 @@ def _make_evaluator(distance, x, sample_rate, plugins, model, target, **kw):
         return engine.MelMrstftEvaluator(x, sample_rate, plugins, target)
     if distance in _PREFILTERED_DISTANCES:
         return engine.PrefilteredMrstftEvaluator(x, sample_rate, plugins, target, kind=_PREFILTERED_DISTANCES[distance], prefilter="aw")
+    if distance in _WAVEFORM_DISTANCES:
+        kind, prefilter = _WAVEFORM_DISTANCES[distance]
+        return engine.WaveformEvaluator(x, sample_rate, plugins, target, kind=kind, prefilter=prefilter)
     return engine.PopulationEvaluator(x, sample_rate, plugins, model, target, **kw)
 
 
@@ -695,7 +703,9 @@ def run_staged_es(
     render the target's channel count, and savepop is refused as run_es refuses it for this objective.  distance="mrstft-sd"
     is the same with the sum / difference distance: every stage's sub-chain must render 2 channels; distance="mrstft-mel" is
     distance="mrstft" on mel-band sums of the magnitudes (engine.MelMrstftEvaluator).  "mrstft-aw", "mrstft-sd-aw" and "mrstft-mel-aw"
-    are those three on rows that went through the A-weighting FIR of the sample rate first (engine.PrefilteredMrstftEvaluator)."""
+    are those three on rows that went through the A-weighting FIR of the sample rate first (engine.PrefilteredMrstftEvaluator).
+    "esr", "snr", "sisdr", "logcosh" and their "-aw" forms score every stage's render with a waveform distance
+    (engine.WaveformEvaluator) under the same rules."""
     _check_distance(distance, sample_rate)
     savepop = bool(savepop or save_pop)
     names = list(plugins.keys())
@@ -821,7 +831,11 @@ def run_es_batch(
 
     distance="mrstft-aw", "mrstft-sd-aw", "mrstft-mel-aw": the three above with render and target A-weighted first -- auraloss's
     perceptual_weighting=True, the 101-tap FIR of features.mrstft_prefilter("aw", sample_rate), applied in the loss kernel's loader
-    (engine.PrefilteredMrstftEvaluator); the 2-channel rule and the empty-band rule of their plain forms hold."""
+    (engine.PrefilteredMrstftEvaluator); the 2-channel rule and the empty-band rule of their plain forms hold.
+
+    distance="esr", "snr", "sisdr", "logcosh" and each with "-aw": the waveform distances of engine.WaveformEvaluator (error-to-signal
+    ratio, SNR, scale-invariant SDR, log-cosh; "-aw": behind the same A-weighting FIR), sample against sample, on both forms and on
+    every path of the list form, under the rules of distance="mrstft"; any channel count the chain renders."""
     _check_distance(distance, sample_rate)
     ragged = isinstance(input_audios, (list, tuple)) or isinstance(target_audios, (list, tuple))
     if ragged:
