@@ -380,6 +380,12 @@ size_t stito_conv3x3_workspace_bytes(int n, int H, int W, int cin, int cout, int
 int stito_conv3x3_bn_relu_ws(const float *in_dev, const float *packed_w_dev, const float *scale_dev,
                              const float *shift_dev, float *out_dev, int n, int H, int W, int cin, int cout,
                              int pool, int algo, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Test hook, exported but NOT part of the declared ABI (so not in st_ito/_hip.py's SIGNATURES either: the bit fixtures of
+ * tests/golden/make_w43_epilogue_sha.py are recorded with libraries from before it existed, which must still load):
+ *     int stito_conv3x3_bn_relu_ws_amax(<the arguments of stito_conv3x3_bn_relu_ws>, unsigned *amax_out_dev);
+ * the same launch, also reporting what the trunk hands from one layer to the next: amax_out_dev = n words the caller zeroed,
+ * word s = the bit pattern of stream s's largest output (>= 0 after ReLU), or NULL.  STITO_E_INVALID for an algorithm that
+ * does not report maxima (the F(4x4,3x3) family and STITO_CONV_WINOGRAD_F2_REG do). */
 
 /* ---- hand-crafted features: st_ito/features.py (alternative metrics of the evaluation harness) ---- */
 /* compute_rms_energy (features.py:235-245) and compute_crest_factor (248-264) of (n_items, channels, n) audio

@@ -1241,6 +1241,14 @@ extern "C" int stito_conv3x3_bn_relu_ws(const float *in_dev, const float *packed
                                      workspace_bytes, (hipStream_t)stream, nullptr, nullptr, g_wino_trace});
 }
 
+extern "C" int stito_conv3x3_bn_relu_ws_amax(const float *in_dev, const float *packed_w_dev, const float *scale_dev,
+                                             const float *shift_dev, float *out_dev, int n, int H, int W, int cin, int cout,
+                                             int pool, int algo, void *workspace_dev, size_t workspace_bytes, void *stream,
+                                             unsigned *amax_out_dev) {
+    return conv3x3_ws(algo, ConvArgs{in_dev, packed_w_dev, scale_dev, shift_dev, out_dev, ConvShape{n, H, W, cin, cout}, pool != 0, workspace_dev,
+                                     workspace_bytes, (hipStream_t)stream, nullptr, amax_out_dev, g_wino_trace});
+}
+
 static void cnn14_dims(int64_t T, int M, int H[7], int W[7]) {
     H[0] = (int)T; W[0] = M;
     for (int b = 1; b <= 5; ++b) { H[b] = H[b - 1] / 2; W[b] = W[b - 1] / 2; }

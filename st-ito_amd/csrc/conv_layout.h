@@ -48,7 +48,8 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {  // a + (-b): exact,
 // LDS-DMA: 16 B per lane, global (sbase SGPR pair, wave-uniform, + voff per-lane byte offset) -> LDS at M0 + lane * 16,
 // no VGPR round trip and no VALU instruction.  M0 is not saved: nothing else in the kernels that use this reads it
 // (gfx950 LDS instructions do not, and they have no movrel / sendmsg / interp); hipcc rejects "m0" in a clobber list as
-// reserved, so that is checked by inspection of the ISA (grep m0: only these statements write it).
+// reserved, so that is checked by inspection of the ISA (grep m0: only these statements and w43_xch_put of conv_wino43.hip, which
+// sets it in front of its own stores in the same way, write it).
 __device__ __forceinline__ void glds16_m0(const float *sbase, unsigned voff, unsigned lds_byte_addr) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
 }

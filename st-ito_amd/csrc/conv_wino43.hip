@@ -30,10 +30,10 @@
 //          coefficients (4 ds_read_b64 + 4 packed VALU per column), then the column combination (12 packed VALU) and 6
 //          ds_write_b64.
 // One barrier per chunk in a rotated loop (barrier(k) sits after the operand reads of chunk k's last block group).
-// Epilogue: the 36 positions of an output meet in three passes over the position rows {1,2}, {3,4}, {0,5}: the owning
-// waves write those accumulators to LDS (12 x 32 x 64 floats), thread (tile, channel quad) reduces each row over j
-// (column half of A^T M A) and accumulates its contribution to the 4x4 outputs; then BN + ReLU (+ pool) and 16-byte
-// stores into the channel-blocked activation layout.
+// Epilogue: the 36 positions of an output meet in three passes: every wave writes three of its nine accumulator blocks
+// to LDS (12 x 32 x 64 floats per pass), thread (tile, channel quad) reduces each position row over j (column half of
+// A^T M A, a half row per wave pair and pass) and, after the last pass, sums the six rows into the 4x4 outputs; then
+// BN + ReLU (+ pool) and 16-byte stores into the channel-blocked activation layout.
 #include "conv_layout.h"
 
 #include <cstdlib>
@@ -45,28 +45,45 @@ namespace stito {
 #ifndef W43_CLK
 #define W43_CLK 0  // measurement build (tools/ab_build.sh clk -DW43_CLK=1): the workgroup in the middle of the grid reads s_memtime (shader
                    // clock) and s_memrealtime (constant 100 MHz) at its start and end, the launcher prints the ratio = the clock the part
-                   // really ran at under this kernel; 0 in every build that ships
+                   // really ran at under this kernel; 0 in every build that ships.  The kernels that end in w43_epilogue also stamp its
+                   // start (W43_CLK_EPI) and, inside it, wave 0's shader clocks between the barriers (W43_EP_CLK_*): the wait for the
+                   // other waves' last products, the exchange writes (up to the barrier = the slowest wave's), the reads + arithmetic
+                   // (up to the next pass's barrier), and what is left to the item's end = BN + stores
 #endif
 #if W43_CLK
+static constexpr int W43_CLK_SLOTS = 8;  // words per launch: shader clock start / end, 100 MHz clock start / end, epilogue start, and its three sums
 #define W43_CLK_BEGIN()                                                                                                 \
     const bool clk_on = g.clk != nullptr && blockIdx.x == (gridDim.x >> 1) && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0; \
-    long long clk_c0 = 0, clk_r0 = 0;                                                                                   \
+    long long clk_c0 = 0, clk_r0 = 0, clk_e0 = 0;                                                                       \
     if (clk_on) { clk_c0 = (long long)__builtin_readcyclecounter(); clk_r0 = (long long)__builtin_amdgcn_s_memrealtime(); }
+#define W43_CLK_EPI() if (clk_on) clk_e0 = (long long)__builtin_readcyclecounter();
 #define W43_CLK_END()                                                                                                   \
     if (clk_on && (threadIdx.x & 63) == 0) {                                                                            \
         g.clk[0] = clk_c0; g.clk[1] = (long long)__builtin_readcyclecounter();                                          \
         g.clk[2] = clk_r0; g.clk[3] = (long long)__builtin_amdgcn_s_memrealtime();                                      \
+        g.clk[4] = clk_e0;   /* 0: this kernel has no epilogue stamps */                                                \
     }
+#define W43_EP_CLK_BEGIN()                                                                                              \
+    const bool ep_on = g.clk != nullptr && blockIdx.x == (gridDim.x >> 1) && __builtin_amdgcn_readfirstlane(tid >> 6) == 0; \
+    long long ep_t = 0, ep_sum[3] = {0, 0, 0};                                                                          \
+    if (ep_on) ep_t = (long long)__builtin_readcyclecounter();
+#define W43_EP_CLK_ADD(I)                                                                                               \
+    if (ep_on) { const long long now_ = (long long)__builtin_readcyclecounter(); ep_sum[I] += now_ - ep_t; ep_t = now_; }
+#define W43_EP_CLK_END() if (ep_on && (tid & 63) == 0) { g.clk[5] = ep_sum[0]; g.clk[6] = ep_sum[1]; g.clk[7] = ep_sum[2]; }
 #else
 #define W43_CLK_BEGIN()
+#define W43_CLK_EPI()
 #define W43_CLK_END()
+#define W43_EP_CLK_BEGIN()
+#define W43_EP_CLK_ADD(I)
+#define W43_EP_CLK_END()
 #endif
 static constexpr int W43_THREADS = 512;
 static constexpr int W43_K = 4;                          // input channels per chunk
 static constexpr int W43_U = 36 * 64 * W43_K;            // floats: [pos][cout][4]
 static constexpr int W43_V = 36 * 32 * W43_K;            // floats: [pos][tile][4]
 static constexpr int W43_BUF = W43_U + W43_V;
-static constexpr int W43_XT = 68;                        // exchange: floats per tile row ([pos][tile][64 cout], +4 pad)
+static constexpr int W43_XT = 68;                        // exchange: floats per tile of a position's slot (k_conv_wino43s2: [pos][tile][64 cout], +4 pad; w43_epilogue: w43_xch_row)
 
 // split-precision streaming kernel (k_conv_wino43s): a slab = 8 position slots x 16 input channels of f16 halves hi + lo
 static constexpr int S43_VPART = 8 * 2048;               // bytes: per slot [hi | lo][channel octet 0, 1][32 tiles][8 f16]
@@ -179,76 +196,122 @@ __device__ __forceinline__ unsigned w43_max4(f32x4 v) {
 }
 
 // ---- epilogue (shared by k_conv_wino43 and k_conv_wino43s) ---------------------------------------------------------
-// Y = A^T M A,  A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1].  Three passes over the position rows
-// {1,2}, {3,4}, {0,5} (the pairs whose contributions share sums and differences); reader thread = (tile, channel
-// quad) keeps the 4x4 outputs of its 4 channels (64 VGPRs).  Packed arithmetic on register halves throughout.
-// Wave (pg, nh) owns the accumulators of positions 9 pg .. 9 pg + 8 x 32 tiles x channels nh * 32 .. + 31.
+// Y = A^T M A,  A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1].  Wave (pg, nh) owns the accumulators of
+// positions 9 pg .. 9 pg + 8 x 32 tiles x channels nh * 32 .. + 31.  Three passes; in pass t EVERY wave writes its
+// accumulators 3 t .. 3 t + 2 (12 x 32 x 64 floats per pass, 3 positions from each wave pair: the exchange is LDS stores
+// issued by the wave the barrier waits for, so the work is spread evenly -- passes over whole position rows, {1,2},
+// {3,4}, {0,5} as they are summed, had one wave pair write 9 + 9 + 6 positions while half of the workgroup wrote none).
+// Three consecutive positions of a wave pair are one half (columns 0..2 or 3..5) of a position row; reader thread =
+// (tile, channel quad) keeps a half row's share of the column half of A^T M A (12 VGPRs) until the other half has come,
+// then the row's Z_i (16 VGPRs), and, once all six are there, sums them into the 4x4 outputs of its 4 channels in the
+// order {1,2}, {3,4}, {0,5} (the pairs whose contributions share sums and differences).  Every sum has the operands and
+// the order it has when whole rows are read at once: which pass a position travels in does not touch the result's bits.
+// Packed arithmetic on register halves throughout.  The stores: w43_xch_put.
 // SPLIT: the accumulators carry the power-of-two operand scales of the split-precision kernel: 1 / (u_scale * v_scale(stream))
 // is folded into the BN scale (exact: powers of two).
 #define W43_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+// Exchange slot of one position: 32 rows of 64 floats.  Row (r, nh) is what register r of wave (.., nh)'s accumulator block holds
+// across its 64 lanes -- channels nh * 32 .. + 31 of tile (r & 3) + 8 (r >> 2), then the same of that tile + 4 -- so a register
+// goes out as 64 consecutive dwords: ds_write_addtid_b32 (address = M0 + offset + 4 lane: no address VGPR, and the one LDS store
+// that moves 4 bytes per lane in 2 cycles; the ds_write2_b32 it replaces took 3 per dword and set the exchange's time).  The rows
+// of odd r sit 32 floats off the 64-float grid, behind the even ones: the reader's ds_read_b128 (16 floats each of two
+// neighbouring tiles' two channel halves per lane group) then falls on 64 different banks.
+__host__ __device__ constexpr int w43_xch_row(int r, int nh) { return (r & 1) * (16 * 64 + 32) + ((r >> 1) * 2 + nh) * 64; }
+static_assert(w43_xch_row(15, 1) + 64 <= 32 * W43_XT, "the rows fit the exchange slot");
+// the 16 registers of one accumulator block -> rows (r, nh) of the slot at m0 + OFF (bytes; m0 carries the wave's nh)
+template <int OFF>
+__device__ __forceinline__ void w43_xch_put(const f32x16 &a, unsigned m0) {
+    static_assert(OFF >= 0 && OFF + w43_xch_row(15, 0) * 4 < 65536, "16-bit instruction offset");
+    asm volatile("s_mov_b32 m0, %16\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %0 offset:%17\n\tds_write_addtid_b32 %1 offset:%17+4224\n\t"
+                 "ds_write_addtid_b32 %2 offset:%17+512\n\tds_write_addtid_b32 %3 offset:%17+4736\n\t"
+                 "ds_write_addtid_b32 %4 offset:%17+1024\n\tds_write_addtid_b32 %5 offset:%17+5248\n\t"
+                 "ds_write_addtid_b32 %6 offset:%17+1536\n\tds_write_addtid_b32 %7 offset:%17+5760\n\t"
+                 "ds_write_addtid_b32 %8 offset:%17+2048\n\tds_write_addtid_b32 %9 offset:%17+6272\n\t"
+                 "ds_write_addtid_b32 %10 offset:%17+2560\n\tds_write_addtid_b32 %11 offset:%17+6784\n\t"
+                 "ds_write_addtid_b32 %12 offset:%17+3072\n\tds_write_addtid_b32 %13 offset:%17+7296\n\t"
+                 "ds_write_addtid_b32 %14 offset:%17+3584\n\tds_write_addtid_b32 %15 offset:%17+7808"
+                 :
+                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(a[8]), "v"(a[9]), "v"(a[10]),
+                   "v"(a[11]), "v"(a[12]), "v"(a[13]), "v"(a[14]), "v"(a[15]), "s"(m0), "n"(OFF)
+                 : "memory");
+}
+static_assert(w43_xch_row(1, 0) * 4 == 4224 && w43_xch_row(2, 0) * 4 == 512 && w43_xch_row(15, 0) * 4 == 7808, "w43_xch_put spells the row offsets out");
 template <int TTW, bool POOL, bool SPLIT>
 __device__ __forceinline__ void w43_epilogue(float *smem, f32x16 (&acc)[9], const int tid, const int pg, const int nh,
                                              const Wino43Geom &g, const int n0, const int vtr0, const int tc0,
                                              const float *__restrict__ scale, const float *__restrict__ shift,
                                              float *__restrict__ out, const float u_inv, const unsigned *__restrict__ amax) {
-    const int lane = tid & 63, half = lane >> 5, l31 = lane & 31;
 #define A4(a, b) __builtin_shufflevector(pk_add(P2(a, 0), P2(b, 0)), pk_add(P2(a, 1), P2(b, 1)), 0, 1, 2, 3)
 #define S4(a, b) __builtin_shufflevector(pk_sub(P2(a, 0), P2(b, 0)), pk_sub(P2(a, 1), P2(b, 1)), 0, 1, 2, 3)
 #define F4(c2, a, b) __builtin_shufflevector(pk_fma(c2, P2(a, 0), P2(b, 0)), pk_fma(c2, P2(a, 1), P2(b, 1)), 0, 1, 2, 3) /* c a + b */
-    float *xch = smem;                      // [12 positions of the pass][32 tiles][W43_XT]
+    float *xch = smem;                      // [12 positions of the pass][W43_XT * 32 floats: w43_xch_row]
     constexpr int XP = 32 * W43_XT;
+    static_assert((3 * XP + w43_xch_row(0, 1)) * 4 + 4 * XP * 4 < 65536, "M0 of w43_xch_put: 16 bits (the exchange starts the workgroup's LDS)");
     const int e_quad = tid & 15, e_tile = tid >> 4;
+    // writer: M0 = byte address of the wave's first row in slot pg;  reader: float offset of (tile, channel quad) inside a slot
+    const unsigned x_m0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)xch + (unsigned)(pg * XP + w43_xch_row(0, nh)) * 4u;
+    const int x_rd = w43_xch_row((e_tile & 3) + 4 * (e_tile >> 3), e_quad >> 3) + ((e_tile >> 2) & 1) * 32 + (e_quad & 7) * 4;
     const f32x2 k2 = {2.f, 2.f}, k4 = {4.f, 4.f}, k8 = {8.f, 8.f};
-    f32x4 Yo[4][4];
+    f32x4 Yo[4][4], Z[6][4];                // Z[i]: column half of position row i, kept until the row half below
+    f32x4 lo3[6][3], hi3[6][3];             // row i's columns 0..2 as (m0 + s12, d12, s12), its columns 3..5 as (s34, d34, m5)
+    W43_EP_CLK_BEGIN()
 #pragma unroll
     for (int pass = 0; pass < 3; ++pass) {
         W43_BARRIER()  // the main loop's (or the previous pass's) LDS reads are done
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            const int p = 9 * pg + q;  // wave-uniform
-            // exchange slot of position p in this pass: rows {1,2} -> p - 6, rows {3,4} -> p - 18, rows {0,5} -> p or p - 24
-            const int slot = pass == 0 ? p - 6 : pass == 1 ? p - 18 : (p < 6 ? p : p - 24);
-            const bool mine = pass == 0 ? (p >= 6 && p < 18) : pass == 1 ? (p >= 18 && p < 30) : (p < 6 || p >= 30);
-            if (mine) {
-                float *xp = xch + slot * XP + nh * 32 + l31;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int trow = (r & 3) + 8 * (r >> 2) + 4 * half;
-                    xp[trow * W43_XT] = acc[q][r];
-                }
-            }
-        }
+        W43_EP_CLK_ADD(pass == 0 ? 0 : 2)
+        if (pass == 0) asm volatile("s_nop 15\n\ts_nop 15");  // (w43_xch_put is opaque to hipcc's MFMA hazard handling: the last products retire here)
+        // position 9 pg + 3 pass + k -> exchange slot 4 k + pg (M0 and the instruction offset are 16 bits each: slot 8 + pg through M0)
+        w43_xch_put<0>(acc[3 * pass + 0], x_m0);
+        w43_xch_put<4 * XP * 4>(acc[3 * pass + 1], x_m0);
+        w43_xch_put<4 * XP * 4>(acc[3 * pass + 2], x_m0 + 4 * XP * 4);
         W43_BARRIER()
-        f32x4 Z[2][4];
+        W43_EP_CLK_ADD(1)
 #pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-            f32x4 m[6];
+        for (int wp = 0; wp < 4; ++wp) {    // the three positions of wave pair wp: columns j0 .. j0 + 2 of row i
+            const int i = (9 * wp + 3 * pass) / 6, j0 = (9 * wp + 3 * pass) % 6;
+            f32x4 m[3];
 #pragma unroll
-            for (int j = 0; j < 6; ++j) m[j] = *(const f32x4 *)(xch + (ii * 6 + j) * XP + e_tile * W43_XT + e_quad * 4);
-            // column half: Z[c] = sum_j M[i][j] A[j][c]
-            const f32x4 s12 = A4(m[1], m[2]), d12 = S4(m[1], m[2]), s34 = A4(m[3], m[4]), d34 = S4(m[3], m[4]);
-            Z[ii][0] = A4(A4(m[0], s12), s34);
-            Z[ii][1] = F4(k2, d34, d12);
-            Z[ii][2] = F4(k4, s34, s12);
-            Z[ii][3] = A4(F4(k8, d34, d12), m[5]);
-        }
-        // row half: Y[r][c] += A^T[r][i] Z_i[c]
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (pass == 0) {         // rows 1, 2: A^T columns (1,1,1,1) and (1,-1,1,-1); first pass: initialises Y
-                const f32x4 sm = A4(Z[0][c], Z[1][c]), df = S4(Z[0][c], Z[1][c]);
-                Yo[0][c] = sm; Yo[1][c] = df; Yo[2][c] = sm; Yo[3][c] = df;
-            } else if (pass == 1) {  // rows 3, 4: (1,2,4,8) and (1,-2,4,-8)
-                const f32x4 sm = A4(Z[0][c], Z[1][c]), df = S4(Z[0][c], Z[1][c]);
-                Yo[0][c] = A4(Yo[0][c], sm); Yo[1][c] = F4(k2, df, Yo[1][c]); Yo[2][c] = F4(k4, sm, Yo[2][c]); Yo[3][c] = F4(k8, df, Yo[3][c]);
-            } else {                 // rows 0, 5: (1,0,0,0) and (0,0,0,1)
-                Yo[0][c] = A4(Yo[0][c], Z[0][c]); Yo[3][c] = A4(Yo[3][c], Z[1][c]);
+            for (int k = 0; k < 3; ++k) m[k] = *(const f32x4 *)(xch + (4 * k + wp) * XP + x_rd);
+            if (j0 == 0) {
+                const f32x4 s12 = A4(m[1], m[2]);
+                lo3[i][0] = A4(m[0], s12); lo3[i][1] = S4(m[1], m[2]); lo3[i][2] = s12;
+            } else {
+                hi3[i][0] = A4(m[0], m[1]); hi3[i][1] = S4(m[0], m[1]); hi3[i][2] = m[2];
             }
         }
+        // column half of the rows that are complete now: Z[c] = sum_j M[i][j] A[j][c]
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            if (pass == (i % 3 == 0 ? 1 : 2)) {
+                const f32x4 d12 = lo3[i][1], s12 = lo3[i][2], s34 = hi3[i][0], d34 = hi3[i][1];
+                Z[i][0] = A4(lo3[i][0], s34);
+                Z[i][1] = F4(k2, d34, d12);
+                Z[i][2] = F4(k4, s34, s12);
+                Z[i][3] = A4(F4(k8, d34, d12), hi3[i][2]);
+            }
+        }
+    }
+    // row half: Y[r][c] = sum_i A^T[r][i] Z_i[c], summed in the order rows {1,2}, {3,4}, {0,5} (the order of the sums is part of the
+    // result's bits; the order of the passes above is not)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        {   // rows 1, 2: A^T columns (1,1,1,1) and (1,-1,1,-1)
+            const f32x4 sm = A4(Z[1][c], Z[2][c]), df = S4(Z[1][c], Z[2][c]);
+            Yo[0][c] = sm; Yo[1][c] = df; Yo[2][c] = sm; Yo[3][c] = df;
+        }
+        {   // rows 3, 4: (1,2,4,8) and (1,-2,4,-8)
+            const f32x4 sm = A4(Z[3][c], Z[4][c]), df = S4(Z[3][c], Z[4][c]);
+            Yo[0][c] = A4(Yo[0][c], sm); Yo[1][c] = F4(k2, df, Yo[1][c]); Yo[2][c] = F4(k4, sm, Yo[2][c]); Yo[3][c] = F4(k8, df, Yo[3][c]);
+        }
+        // rows 0, 5: (1,0,0,0) and (0,0,0,1)
+        Yo[0][c] = A4(Yo[0][c], Z[0][c]); Yo[3][c] = A4(Yo[3][c], Z[5][c]);
     }
 #undef A4
 #undef S4
 #undef F4
+    W43_EP_CLK_ADD(2)
+    W43_EP_CLK_END()
     // BN + ReLU (+ 2x2 average pool), 16-byte stores (4 channels) into NC8HW8
     {
         const int co = n0 + e_quad * 4;
@@ -723,7 +786,7 @@ __global__ __launch_bounds__(W43_THREADS, MODE >= 2 ? 4 : 2) void k_conv_wino43(
         }
     }
     W43_STAMP(2)
-
+    W43_CLK_EPI()
     w43_epilogue<TTW, POOL, false>(smem, acc, tid, pg, nh, g, n0, vtr0, tc0, scale, shift, out, 1.0f, nullptr);
     W43_CLK_END()
     W43_STAMP(3)
@@ -860,6 +923,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s(const char *__rest
         S43_PERIOD(12, sl + 12) S43_PERIOD(13, sl + 13) S43_PERIOD(14, sl + 14) S43_PERIOD(15, sl + 15) S43_PERIOD(16, sl + 16) S43_PERIOD(17, sl + 17)
     }
     S43_MFMA_P(8, alP, bhP) S43_MFMA_P(8, ahP, blP) S43_MFMA_P(8, ahP, bhP)  // the last period's second block (n_slabs % 18 == 0: accumulator 8)
+    W43_CLK_EPI()
     w43_epilogue<TTW, POOL, true>(smem, acc, tid, pg, nh, g, n0, vtr0, tc0, scale, shift, out, u_inv_p[0], amax);
     W43_CLK_END()
 }
@@ -1552,14 +1616,15 @@ static double wino43_issued_flops(const ConvShape &c, bool pool) {
 
 #if W43_CLK
 // a ring of 256 launches, no synchronisation (the launches stay back to back); dumped when the process exits: the LAST launch of
-// every (kernel, shape), i.e. the clock after that kernel has run for as long as the caller kept launching it
+// every (kernel, shape), i.e. the clock after that kernel has run for as long as the caller kept launching it (STITO_W43_CLK_ALL=1: every
+// launch in the ring, for the spread from one launch to the next)
 struct W43ClkLog { char what[32]; int H, W, Cin, Cout; };
 static long long *w43_clk_ring = nullptr;
 static W43ClkLog w43_clk_log[256];
 static int w43_clk_n = 0;
 static void w43_clk_dump() {
     if (w43_clk_n == 0) return;
-    static long long v[256 * 4];
+    static long long v[256 * W43_CLK_SLOTS];
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(v, w43_clk_ring, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
     const int first = w43_clk_n > 256 ? w43_clk_n - 256 : 0;
     for (int i = first; i < w43_clk_n; ++i) {
@@ -1569,19 +1634,22 @@ static void w43_clk_dump() {
             const W43ClkLog &m = w43_clk_log[j & 255];
             last = !(m.H == l.H && m.W == l.W && m.Cin == l.Cin && m.Cout == l.Cout && strcmp(m.what, l.what) == 0);
         }
-        if (!last) continue;
-        const long long *q = v + (i & 255) * 4;
+        if (!last && getenv("STITO_W43_CLK_ALL") == nullptr) continue;
+        const long long *q = v + (i & 255) * W43_CLK_SLOTS;
         const double us = (double)(q[3] - q[2]) / 100.0;
         fprintf(stderr, "[stito clock] %-28s %dx%d %d->%d: workgroup in the middle of the grid ran %.1f us at %.0f MHz (launch %d)\n", l.what, l.H, l.W,
                 l.Cin, l.Cout, us, us > 0 ? (double)(q[1] - q[0]) / us : 0.0, i);
+        if (q[4] != 0)  // shader clocks of wave 0: the item, its epilogue, and the epilogue's parts (W43_EP_CLK_*)
+            fprintf(stderr, "[stito clock] %-28s %dx%d %d->%d: item %lld cycles, epilogue %lld = entry wait %lld + exchange writes %lld + reads and sums %lld + BN and stores %lld (launch %d)\n",
+                    l.what, l.H, l.W, l.Cin, l.Cout, q[1] - q[0], q[1] - q[4], q[5], q[6], q[7], q[1] - q[4] - q[5] - q[6] - q[7], i);
     }
 }
 static long long *w43_clk_buf() {
     if (w43_clk_ring == nullptr) {
-        if (hipMalloc(&w43_clk_ring, 256 * 4 * sizeof(long long)) != hipSuccess) return nullptr;
+        if (hipMalloc(&w43_clk_ring, 256 * W43_CLK_SLOTS * sizeof(long long)) != hipSuccess) return nullptr;
         atexit(w43_clk_dump);
     }
-    return w43_clk_ring + (w43_clk_n & 255) * 4;
+    return w43_clk_ring + (w43_clk_n & 255) * W43_CLK_SLOTS;
 }
 static void w43_clk_report(const char *what, const ConvShape &c, hipStream_t) {
     W43ClkLog &l = w43_clk_log[w43_clk_n & 255];
