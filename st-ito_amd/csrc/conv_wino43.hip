@@ -48,10 +48,15 @@ namespace stito {
                    // really ran at under this kernel; 0 in every build that ships.  The kernels that end in w43_epilogue also stamp its
                    // start (W43_CLK_EPI) and, inside it, wave 0's shader clocks between the barriers (W43_EP_CLK_*): the wait for the
                    // other waves' last products, the exchange writes (up to the barrier = the slowest wave's), the reads + arithmetic
-                   // (up to the next pass's barrier), and what is left to the item's end = BN + stores
+                   // (up to the next pass's barrier), and what is left to the item's end = BN + stores.  k_conv_wino43s3 stamps its
+                   // row epilogues instead (W43_S3_CLK_*, waves 0 and 4 = one of each issuing set): summed over the sweeps of rows
+                   // 0 .. 4, the last barrier of the sweep to the last partial store issued, from there to the first barrier passed
+                   // in the next sweep, and the time at the vmcnt(0) of the next sweep's first two periods (one per set); for row 5,
+                   // summed over the eight output groups, loads issued / data there / combined and stores issued
 #endif
 #if W43_CLK
-static constexpr int W43_CLK_SLOTS = 8;  // words per launch: shader clock start / end, 100 MHz clock start / end, epilogue start, and its three sums
+static constexpr int W43_CLK_SLOTS = 24;  // words per launch: shader clock start / end, 100 MHz clock start / end, epilogue start, and its three sums;
+                                          // k_conv_wino43s3: 8 .. 14 wave 0's six sums and its row-5 start, 16 .. 22 wave 4's
 #define W43_CLK_BEGIN()                                                                                                 \
     const bool clk_on = g.clk != nullptr && blockIdx.x == (gridDim.x >> 1) && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0; \
     long long clk_c0 = 0, clk_r0 = 0, clk_e0 = 0;                                                                       \
@@ -70,7 +75,39 @@ static constexpr int W43_CLK_SLOTS = 8;  // words per launch: shader clock start
 #define W43_EP_CLK_ADD(I)                                                                                               \
     if (ep_on) { const long long now_ = (long long)__builtin_readcyclecounter(); ep_sum[I] += now_ - ep_t; ep_t = now_; }
 #define W43_EP_CLK_END() if (ep_on && (tid & 63) == 0) { g.clk[5] = ep_sum[0]; g.clk[6] = ep_sum[1]; g.clk[7] = ep_sum[2]; }
+// k_conv_wino43s3: s3_sum[0..2] rows 0 .. 4 (stores issued, to the next sweep's first barrier, at its first two vmcnt(0)), [3..5] row 5
+// (loads issued, data there, stores issued), [6] the cycle row 5's epilogue began at.  A stamp is a scalar clock read behind
+// s_waitcnt lgkmcnt(0): it does not wait for stores or loads, so "issued" is when the wave has handed the last one to the memory pipe.
+#define W43_S3_CLK_BEGIN()                                                                                              \
+    const int s3_wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                  \
+    const bool s3_on = g.clk != nullptr && blockIdx.x == (gridDim.x >> 1) && (s3_wv & 3) == 0;                           \
+    long long s3_t = 0, s3_sum[7] = {0, 0, 0, 0, 0, 0, 0};
+#define W43_S3_CLK_MARK() if (s3_on) s3_t = (long long)__builtin_readcyclecounter();
+#define W43_S3_CLK_ADD(I)                                                                                               \
+    if (s3_on) { const long long now_ = (long long)__builtin_readcyclecounter(); s3_sum[I] += now_ - s3_t; s3_t = now_; }
+#define W43_S3_CLK_ROW5() if (s3_on) s3_sum[6] = (long long)__builtin_readcyclecounter();
+// in the period: s3_head counts down the first two periods of a sweep that follows a row epilogue (0 everywhere else): they hold
+// each set's first vmcnt(0) behind its partial stores (set 1: the first period, set 0: the second)
+#define W43_S3_CLK_SWEEP(FOLLOWS) int s3_head = (FOLLOWS) ? 2 : 0; long long s3_w = 0;
+#define W43_S3_CLK_WAIT0() if (s3_on && s3_head != 0) s3_w = (long long)__builtin_readcyclecounter();
+#define W43_S3_CLK_WAIT1() if (s3_on && s3_head != 0) s3_sum[2] += (long long)__builtin_readcyclecounter() - s3_w;
+#define W43_S3_CLK_HEAD()  if (s3_head == 2) { W43_S3_CLK_ADD(1) } if (s3_head != 0) --s3_head;
+#define W43_S3_CLK_TOUCH(X) asm volatile("" : : "v"(X));   // the compiler's wait for X's load stands in front of this
+#define W43_S3_CLK_END()                                                                                                \
+    if (s3_on && (threadIdx.x & 63) == 0) {                                                                             \
+        _Pragma("unroll") for (int i_ = 0; i_ < 7; ++i_) g.clk[8 + 2 * s3_wv + i_] = s3_sum[i_];                        \
+    }
 #else
+#define W43_S3_CLK_BEGIN()
+#define W43_S3_CLK_MARK()
+#define W43_S3_CLK_ADD(I)
+#define W43_S3_CLK_ROW5()
+#define W43_S3_CLK_SWEEP(FOLLOWS)
+#define W43_S3_CLK_WAIT0()
+#define W43_S3_CLK_WAIT1()
+#define W43_S3_CLK_HEAD()
+#define W43_S3_CLK_TOUCH(X)
+#define W43_S3_CLK_END()
 #define W43_CLK_BEGIN()
 #define W43_CLK_EPI()
 #define W43_CLK_END()
@@ -1172,9 +1209,13 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s2(const char *__res
 // is assembled through a workgroup-private f32 scratch area (1.25 MB, written and read back by the same lanes): a wave owns
 // all six positions of the row for its sub-tile, so the column combination Z_i[c] = sum_j M[i][j] A[j][c] happens in registers
 // -- NO exchange through LDS, no barrier in the epilogue -- and rows 0..4 just store their four Z values per output (stores
-// only: nothing waits; accumulating the 16 outputs instead was 3.4 x the traffic and a load-add-store chain per sweep: measured,
-// the first version); the sweep of row 5 reads the twenty values back, one output column at a time, combines the rows, and
+// only; accumulating the 16 outputs instead was 3.4 x the traffic and a load-add-store chain per sweep: measured, the first
+// version); the sweep of row 5 reads the twenty values back, one output column pair at a time, combines the rows, and
 // finishes (operand scales, BN, ReLU, pool, stores).
+// What the row epilogues cost (W43_CLK stamps of waves 0 and 4, 512 streams, profiles/w43s3_epilogue_ab.txt): a row's 256 KB of
+// partial stores take 4 100 - 7 200 cycles to ISSUE -- the CU's 64 B / clk store path, 4 096 cycles, with the whole workgroup in
+// the epilogue -- and are gone by then: the vmcnt(0) of the next sweep's first two periods, which on gfx950 count them beside the
+// slab copies they guard, pass in ~20 cycles each.  Moving those waits buys nothing and was not done.
 // Slab = 3 positions (half a row) x 16 channels x (128 tiles | 128 couts) x (hi, lo) = 48 KB: [input part 24 KB | weight part
 // 24 KB], position jj at 8 KB: [hi 4 KB | lo 4 KB], each [channel octet][128][8 f16]; ring of three, two wave sets issuing on
 // alternate periods as above; two periods per 16 channels.  MFMA A operand = weights (rows = couts), B = input (columns =
@@ -1216,6 +1257,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
     const int m_quad = ((gi / n_ctg) * (32 / a) + r / a) * xm + (xcd % xm);
     if (m_quad >= g.n_mblocks) return;
     W43_CLK_BEGIN()
+    W43_S3_CLK_BEGIN()
     const int nP = g.Cin >> 3;   // periods per sweep: two per 16 input channels
     const int sw_lo = SWSPLIT ? my_sweep : 0, sw_hi = SWSPLIT ? my_sweep + 1 : 6;   // the sweeps this workgroup runs
     const int sl_end = sw_hi * nP;                                                  // ... and the end of its slab stream
@@ -1224,7 +1266,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
     const unsigned ldsw = lds0 + (unsigned)w4 * 1024u;
     const char *v_rd = (const char *)smem + (oct * 128 + th * 64 + l31) * 16;               // + jj * 8192 (+ 4096: lo) + blk * 512
     const char *u_rd = (const char *)smem + S43B_PART + (oct * 128 + cq * 32 + l31) * 16;   // + jj * 8192 (+ 4096: lo)
-    f32x4 *my_partial = partial + (int64_t)b * (8 * 2 * 4 * 20 * 64) + wv * (2 * 4 * 20 * 64) + lane;  // [wave][blk][quad][row 0..4][c][lane]
+    const char *part_wv = (const char *)(partial + (int64_t)b * S43C_PARTIAL + wv * (2 * 4 * 20 * 64));  // [wave][blk][quad][row 0..4][c][lane]: this wave's (uniform)
     const float u_inv = u_inv_p[0];
 
     f32x16 acc[12];   // [position j of the row][tile panel]
@@ -1249,8 +1291,9 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
             S43_MFMA(a0_ + 2 * q_, ul_, vh0_) S43_MFMA(a0_ + 2 * q_ + 1, ul_, vh1_)   /* k_conv_wino43s2: the same bits */ \
             S43_MFMA(a0_ + 2 * q_, uh_, vh0_) S43_MFMA(a0_ + 2 * q_ + 1, uh_, vh1_)                       \
         }                                                                                                 \
-        if (!mine_) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                      \
+        if (!mine_) { W43_S3_CLK_WAIT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); W43_S3_CLK_WAIT1() }   \
         W43_BARRIER()                                                                                     \
+        W43_S3_CLK_HEAD()                                                                                 \
     }
 
     // this lane's two tiles (one per tile panel): map position, validity, stream, BN scale with the operand scales folded in
@@ -1282,6 +1325,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
         for (int q = 0; q < 12; ++q)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[q][i] = 0.0f;
+        W43_S3_CLK_SWEEP(sweep > sw_lo)
         // the six rows' slabs follow one another in both streams: ONE stream of 6 nP periods, the ring keeps filling through the
         // epilogues (which touch neither LDS nor barriers); nP % 2 == 0; the ring position is a run-time value (three loop bodies
         // for it cost registers)
@@ -1291,6 +1335,7 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
             S43C_PERIOD(1, sl + 1, buf)
             buf = buf == 2 ? 0 : buf + 1;
         }
+        W43_S3_CLK_MARK()
         // ---- this row's column combination Z[c] = sum_j M[row][j] A[j][c] (c = 0..3) goes to the scratch area (rows 0..4: stores
         // only, nothing waits for them); the sweep of row 5 reads the five others back, one output column at a time, and finishes:
         // Y[r][c] = sum_i A[i][r] Z_i[c],  A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1] ------------------------------
@@ -1304,16 +1349,27 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
             Z_[2][e] = 4.f * s34 + s12;                                                                   \
             Z_[3][e] = (8.f * d34 + d12) + m5;                                                            \
         }
+        // Addresses in the scratch area: the wave's uniform base (scalar registers) + a constant + this lane's 16 bytes.  The lane
+        // offset is made opaque HERE, per sweep: written as my_partial[constant], the 32 + 160 addresses are loop invariants, were
+        // hoisted in front of the first sweep as 64-bit register pairs and spilled there (~190 scratch stores per item), and every
+        // one came back in the epilogues through a scratch load behind a vmcnt(0) -- which also waits for the partial loads and
+        // output stores issued before it: row 5 ran as ~160 dependent round trips (W43_CLK stamps, profiles/w43s3_epilogue_ab.txt:
+        // 230 000 - 300 000 cycles to ISSUE its loads, 14 000 - 22 000 waiting for their data).
+        unsigned pofs = (unsigned)lane * 16u;
+        asm volatile("" : "+v"(pofs));
+#define S43C_PART(BYTES) ((f32x4 *)(part_w + (BYTES) + (size_t)pofs))   /* [blk][quad][row 0..4][c]: 1 KB each, + the lane */
         if (sweep < 5) {
+            const char *part_w = part_wv + sweep * 4096;
 #pragma unroll
             for (int bg = 0; bg < 8; ++bg) {
                 W43_FENCE()
                 f32x4 Z[4];
                 S43C_Z(bg >> 2, bg & 3, Z)
-                f32x4 *pt = my_partial + bg * (5 * 4 * 64);   // [row 0..4][c][lane]
 #pragma unroll
-                for (int c = 0; c < 4; ++c) pt[(sweep * 4 + c) * 64] = Z[c];
+                for (int c = 0; c < 4; ++c) *S43C_PART(bg * 20480 + c * 1024) = Z[c];
             }
+            W43_FENCE()
+            W43_S3_CLK_ADD(0)
             if (SWSPLIT) {   // publish this row: every thread's stores, then the count
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 W43_BARRIER()
@@ -1326,73 +1382,103 @@ __global__ __launch_bounds__(W43_THREADS) void k_conv_wino43s3(const char *__res
                 W43_BARRIER()
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             }
-            // the last row: all eight Z sets first (the accumulators are dead behind them: 128 registers for the loads that follow --
-            // a (panel, quad)'s twenty stored values in flight at once; five at a time was 32 dependent round trips to HBM per workgroup)
+            // the last row: all eight Z sets first (the accumulators are dead behind them: 128 registers, 16 fewer with every group
+            // finished, for the loads that follow)
             f32x4 Zl[8][4];
 #pragma unroll
             for (int bg = 0; bg < 8; ++bg) { S43C_Z(bg >> 2, bg & 3, Zl[bg]) }
+            W43_S3_CLK_ROW5()
+            // Read back by HALF groups (h = 2 bg + pc: the five rows of an output column pair, 40 registers), the next one's loads
+            // issued ahead of this one's combination: two in flight where a whole group's eighty were waited for before anything
+            // was combined (eight round trips per wave).  Same operands, same order of every sum.  The stream maxima go out once
+            // per tile panel (a maximum does not depend on the order): the comparison against amax_out's current value is a load
+            // whose wait would drain the loads in flight behind every group.
+            constexpr int S43C_ROW5_AHEAD = 4;   // from the third group on: the first two have all of Zl alive and no registers for a second half group
+            const char *part_w = part_wv;
+            f32x4 zr[2][5][2];   // [h % 2][row][column of the pair]
+#define S43C_ROW5_LOAD(H_)                                                                                 \
+            _Pragma("unroll") for (int i = 0; i < 5; ++i)                                                   \
+                _Pragma("unroll") for (int cc = 0; cc < 2; ++cc)                                            \
+                    zr[(H_) & 1][i][cc] = *S43C_PART(((H_) >> 1) * 20480 + (i * 4 + 2 * ((H_) & 1) + cc) * 1024);
+            unsigned smax[2] = {0, 0};
+            f32x4 sc, sh;
+            int co = 0, s_ = 0, tr = 0, tc = 0;
 #pragma unroll
-            for (int bg = 0; bg < 8; ++bg) {
+            for (int h = 0; h < 16; ++h) {
+                const int bg = h >> 1, pc = h & 1, blk = bg >> 2, gq = bg & 3;
                 W43_FENCE()
-                const int blk = bg >> 2, gq = bg & 3;
-                const f32x4 *pt = my_partial + bg * (5 * 4 * 64);
-                f32x4 zr[5][4];
+                W43_S3_CLK_MARK()
+                if (pc == 0) {
+                    // (the same for the output addresses: 16 / 32 per group from this lane's channel and tile position, opaque per group so
+                    // that they are worked out here -- a few integer operations each -- and not kept, as 64-bit pairs, from the item's start)
+                    co = ct * 128 + cq * 32 + 8 * gq + 4 * oct; s_ = t_s[blk]; tr = t_tr[blk]; tc = t_tc[blk];
+                    asm volatile("" : "+v"(co), "+v"(s_), "+v"(tr), "+v"(tc));
+                    sc = *(const f32x4 *)(scale + co);
+                    sh = *(const f32x4 *)(shift + co);
+                    if (t_ok[blk]) sc = sc * (u_inv / w43s_vscale(amax[s_]));
+                    W43_FENCE()   // ahead of the loads below: what this block reads (and reloads) is then not waited for behind them
+                }
+                if (h <= S43C_ROW5_AHEAD) { S43C_ROW5_LOAD(h) }                           // (nobody issued them ahead)
+                if (h >= S43C_ROW5_AHEAD && h + 1 < 16) { S43C_ROW5_LOAD(h + 1) }
+#if W43_CLK
+                W43_FENCE()
+                W43_S3_CLK_ADD(3)
 #pragma unroll
                 for (int i = 0; i < 5; ++i)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) zr[i][c] = pt[(i * 4 + c) * 64];
-                const int co = ct * 128 + cq * 32 + 8 * gq + 4 * oct;
-                f32x4 sc = *(const f32x4 *)(scale + co);
-                const f32x4 sh = *(const f32x4 *)(shift + co);
-                unsigned smax = 0;
-                const int s_ = t_s[blk], tr = t_tr[blk], tc = t_tc[blk];
-                if (t_ok[blk]) sc = sc * (u_inv / w43s_vscale(amax[s_]));
+                    for (int cc = 0; cc < 2; ++cc) W43_S3_CLK_TOUCH(zr[h & 1][i][cc])
+                W43_S3_CLK_ADD(4)
+                W43_FENCE()
+#endif
+                f32x4 y[2][4];   // [column 2 pc + cc][output row]
 #pragma unroll
-                for (int pc = 0; pc < 2; ++pc) {
-                    f32x4 y[2][4];   // [column 2 pc + cc][output row]
+                for (int cc = 0; cc < 2; ++cc) {
+                    const int c = 2 * pc + cc;
+                    const f32x4 *z = &zr[h & 1][0][cc];   // rows two apart
+                    const f32x4 p12 = z[2] + z[4], q12 = z[2] - z[4], p34 = z[6] + z[8], q34 = z[6] - z[8];
+                    y[cc][0] = (z[0] + p12) + p34;
+                    y[cc][1] = 2.f * q34 + q12;
+                    y[cc][2] = 4.f * p34 + p12;
+                    y[cc][3] = (8.f * q34 + q12) + Zl[bg][c];
 #pragma unroll
-                    for (int cc = 0; cc < 2; ++cc) {
-                        const int c = 2 * pc + cc;
-                        const f32x4 p12 = zr[1][c] + zr[2][c], q12 = zr[1][c] - zr[2][c], p34 = zr[3][c] + zr[4][c], q34 = zr[3][c] - zr[4][c];
-                        y[cc][0] = (zr[0][c] + p12) + p34;
-                        y[cc][1] = 2.f * q34 + q12;
-                        y[cc][2] = 4.f * p34 + p12;
-                        y[cc][3] = (8.f * q34 + q12) + Zl[bg][c];
+                    for (int rr = 0; rr < 4; ++rr) y[cc][rr] = __builtin_elementwise_max(y[cc][rr] * sc + sh, (f32x4)(0.0f));
+                }
+                if (t_ok[blk]) {
+                    if (POOL) {
 #pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) y[cc][rr] = __builtin_elementwise_max(y[cc][rr] * sc + sh, (f32x4)(0.0f));
-                    }
-                    if (t_ok[blk]) {
-                        if (POOL) {
+                        for (int pr = 0; pr < 2; ++pr) {
+                            const int oh = 2 * tr + pr, ow = 2 * tc + pc;
+                            if (oh < g.Ho && ow < g.Wo) {
+                                const f32x4 v = (((y[0][2 * pr] + y[1][2 * pr]) + y[0][2 * pr + 1]) + y[1][2 * pr + 1]) * 0.25f;
+                                *(f32x4 *)(out + act_off(s_, co, oh, ow, g.Cout, g.Ho, g.Wo)) = v;
+                                smax[blk] = max(smax[blk], w43_max4(v));
+                            }
+                        }
+                    } else {
 #pragma unroll
-                            for (int pr = 0; pr < 2; ++pr) {
-                                const int oh = 2 * tr + pr, ow = 2 * tc + pc;
-                                if (oh < g.Ho && ow < g.Wo) {
-                                    const f32x4 v = (((y[0][2 * pr] + y[1][2 * pr]) + y[0][2 * pr + 1]) + y[1][2 * pr + 1]) * 0.25f;
-                                    *(f32x4 *)(out + act_off(s_, co, oh, ow, g.Cout, g.Ho, g.Wo)) = v;
-                                    smax = max(smax, w43_max4(v));
+                        for (int cc = 0; cc < 2; ++cc)
+#pragma unroll
+                            for (int rr = 0; rr < 4; ++rr) {
+                                const int hh = 4 * tr + rr, ww = 4 * tc + 2 * pc + cc;
+                                if (hh < g.H && ww < g.W) {
+                                    *(f32x4 *)(out + act_off(s_, co, hh, ww, g.Cout, g.H, g.W)) = y[cc][rr];
+                                    smax[blk] = max(smax[blk], w43_max4(y[cc][rr]));
                                 }
                             }
-                        } else {
-#pragma unroll
-                            for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                                for (int rr = 0; rr < 4; ++rr) {
-                                    const int hh = 4 * tr + rr, ww = 4 * tc + 2 * pc + cc;
-                                    if (hh < g.H && ww < g.W) {
-                                        *(f32x4 *)(out + act_off(s_, co, hh, ww, g.Cout, g.H, g.W)) = y[cc][rr];
-                                        smax = max(smax, w43_max4(y[cc][rr]));
-                                    }
-                                }
-                        }
                     }
                 }
-                // amax_out[s] only grows: a (possibly stale) agent-scope load that already covers smax makes the atomic unnecessary
-                if (g.amax_out != nullptr && t_ok[blk] && smax > __hip_atomic_load(g.amax_out + s_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    atomicMax(g.amax_out + s_, smax);
+                W43_FENCE()
+                W43_S3_CLK_ADD(5)
             }
+            // amax_out[s] only grows: a (possibly stale) agent-scope load that already covers smax makes the atomic unnecessary
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+                if (g.amax_out != nullptr && t_ok[blk] && smax[blk] > __hip_atomic_load(g.amax_out + t_s[blk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    atomicMax(g.amax_out + t_s[blk], smax[blk]);
         }
     }
     W43_CLK_END()
+    W43_S3_CLK_END()
 }
 
 // weights of k_conv_wino43s3: [cout / 128][position row i][period 2 (c / 16) + (j >= 3)] x 24 KB, position j % 3 at 8 KB:
@@ -1639,6 +1725,14 @@ static void w43_clk_dump() {
         const double us = (double)(q[3] - q[2]) / 100.0;
         fprintf(stderr, "[stito clock] %-28s %dx%d %d->%d: workgroup in the middle of the grid ran %.1f us at %.0f MHz (launch %d)\n", l.what, l.H, l.W,
                 l.Cin, l.Cout, us, us > 0 ? (double)(q[1] - q[0]) / us : 0.0, i);
+        if (strstr(l.what, "wino43s3") != nullptr)   // W43_S3_CLK_*: waves 0 and 4 (one of each issuing set)
+            for (int w = 0; w < 2; ++w) {
+                const long long *e = q + 8 + 8 * w;
+                fprintf(stderr, "[stito clock] %-28s %dx%d %d->%d: wave %d: item %lld cycles; rows 0-4 (five sweeps' sum): barrier to last partial store issued %lld, "
+                        "on to the next sweep's first barrier %lld, at its first two vmcnt(0) %lld; row 5 (eight groups' sum, from cycle %lld of the item): "
+                        "loads issued %lld, data there %lld, combined and stores issued %lld (launch %d)\n", l.what, l.H, l.W, l.Cin, l.Cout, 4 * w,
+                        q[1] - q[0], e[0], e[1], e[2], e[6] - q[0], e[3], e[4], e[5], i);
+            }
         if (q[4] != 0)  // shader clocks of wave 0: the item, its epilogue, and the epilogue's parts (W43_EP_CLK_*)
             fprintf(stderr, "[stito clock] %-28s %dx%d %d->%d: item %lld cycles, epilogue %lld = entry wait %lld + exchange writes %lld + reads and sums %lld + BN and stores %lld (launch %d)\n",
                     l.what, l.H, l.W, l.Cin, l.Cout, q[1] - q[0], q[1] - q[4], q[5], q[6], q[7], q[1] - q[4] - q[5] - q[6] - q[7], i);
