@@ -115,7 +115,8 @@ int stito_version(void);
  * stito_mrstft_target_mel, stito_mrstft_loss_mel, stito_mrstft_loss_slots_mel; 9 = the prefiltered MR-STFT distances,
  * stito_mrstft_table_floats_pf, stito_mrstft_workspace_bytes_pf, stito_mrstft_target_pf, stito_mrstft_loss_pf,
  * stito_mrstft_loss_slots_pf; 10 = the waveform distances, stito_waveform_tile_samples, stito_waveform_table_floats,
- * stito_waveform_workspace_bytes, stito_waveform_target, stito_waveform_loss, stito_waveform_loss_slots. */
+ * stito_waveform_workspace_bytes, stito_waveform_target, stito_waveform_loss, stito_waveform_loss_slots; 11 = the FX-Encoder,
+ * stito_fxenc_*. */
 int stito_version_minor(void);
 
 /* LFO of STITO_FX_CHORUS: lfo_dev[n] = sin(phase_n - pi) with juce::dsp::Oscillator's float phase recurrence (phase += 2 pi
@@ -758,6 +759,51 @@ int stito_cmaes_import(void *state_dev, int N, int popsize, int64_t max_iters, c
 int stito_cmaes_status(const void *state_dev, int64_t *status_host, void *stream);
 /* count deviates of (seed, iteration) from element `first` on: z_dev (doubles) and / or bits_dev (the 64-bit integer stage), either NULL */
 int stito_cmaes_normals(uint64_t seed, int64_t iteration, int64_t first, int64_t count, double *z_dev, uint64_t *bits_dev, void *stream);
+
+/* ---- FX-Encoder (ABI 10.11; csrc/fxenc.hip): the reference's second learned embedding, st_ito/models/fx_encoder.py --------------
+ * A stack of one-dimensional convolution layers on (n_items, channels, positions) float32 maps as torch lays them out, then the
+ * mean over positions.  One layer:
+ *     y[b][co][p] = relu(scale[co] * sum_{ci, t} w[co][ci][t] * x[b][ci][reflect(p * stride + t - l_pad)] + shift[co])  (+ x[b][co][p])
+ * p < stito_fxenc_out_len(L, stride) = ceil(L / stride); reflection padding of kernel - 1 samples, l_pad = (kernel - 1) / 2 on
+ * the left and r_pad = kernel - 1 - l_pad on the right (an even kernel pads one more on the right); L > r_pad, else STITO_E_INVALID
+ * naming the layer, before anything is launched.  scale / shift: the eval-mode batch norm and the convolution's bias folded by the
+ * caller in float64, scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) * scale.  dilation must be 1 (STITO_E_UNSUPPORTED).
+ *
+ * Layers with more than two input channels (or a kernel / stride outside {25, 15, 10, 5} x {1, 2, 4}) run as an implicit GEMM on
+ * the f32 matrix pipe, M = cout, N = n_items * out_len, reduction over r = ci * kernel + t in ascending order; the others on the
+ * vector ALU.  Either way every output element is one fixed sequence of operations: an item's results do not depend on the batch
+ * around it, bit for bit.  No atomics, no graph capture, eager launches on `stream`.
+ *
+ * w_packed_dev holds stito_fxenc_packed_floats(cout, cin, kernel, stride) floats.  With bm = stito_fxenc_tile_m(...) > 0 and
+ * bk = stito_fxenc_tile_k(): [ceil(cout / bm)][Rpad][bm], Rpad = cin * kernel rounded up to bk, element (mt, r, mi) =
+ * w[mt * bm + mi][r / kernel][r % kernel], zero where mt * bm + mi >= cout or r >= cin * kernel; 16-byte aligned.  bm == 0: the
+ * plain (cout, cin, kernel) weights.  The packing itself is host code of the caller (st_ito/models/fx_encoder.py), done once per model. */
+typedef struct {
+    int32_t cin, cout, kernel, stride;
+    int32_t dilation;          /* 1 */
+    int32_t residual;          /* 1: + x after the ReLU (cin == cout, stride 1) */
+    const float *w_packed_dev;
+    const float *scale_dev;    /* (cout) */
+    const float *shift_dev;    /* (cout) */
+} stito_fxenc_layer;
+typedef struct {
+    int32_t n_layers;
+    int32_t reserved;
+    const stito_fxenc_layer *layers;   /* host array; layer i + 1 takes layer i's cout channels */
+} stito_fxenc_model;
+int64_t stito_fxenc_out_len(int64_t n_positions, int stride);              /* host only */
+int stito_fxenc_tile_m(int cout, int cin, int kernel, int stride);         /* host only */
+int stito_fxenc_tile_k(void);                                              /* host only */
+size_t stito_fxenc_packed_floats(int cout, int cin, int kernel, int stride); /* host only */
+/* one layer: x_dev (n_items, cin, n_positions) -> y_dev (n_items, cout, out_len); not in place */
+int stito_fxenc_conv1d(const stito_fxenc_layer *layer, const float *x_dev, int n_items, int64_t n_positions, float *y_dev, void *stream);
+/* y_dev (n_items, channels, n_positions) -> out_dev (n_items, channels): the mean over positions, one fixed summation order per row */
+int stito_fxenc_pool(const float *y_dev, int n_items, int channels, int64_t n_positions, float *out_dev, void *stream);
+/* The stack: x_dev (n_items, layers[0].cin, n_samples) -> out_dev (n_items, layers[n - 1].cout).  The workspace holds two buffers of
+ * the largest map any layer writes; stito_fxenc_workspace_bytes returns 0 for arguments the forward would refuse. */
+size_t stito_fxenc_workspace_bytes(const stito_fxenc_model *model, int n_items, int64_t n_samples);
+int stito_fxenc_forward(const stito_fxenc_model *model, const float *x_dev, int n_items, int64_t n_samples, void *workspace_dev,
+                        size_t workspace_bytes, float *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

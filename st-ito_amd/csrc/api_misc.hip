@@ -64,4 +64,4 @@ int device_info(DeviceInfo &info) {
 
 extern "C" const char *stito_last_error(void) { return stito::g_err; }
 extern "C" int stito_version(void) { return 10; }
-extern "C" int stito_version_minor(void) { return 10; }
+extern "C" int stito_version_minor(void) { return 11; }

@@ -82,6 +82,16 @@ def style_distance(a: torch.Tensor, b: torch.Tensor, model, sr: int) -> float:
     return float(torch.stack([torch.cosine_similarity(ea[k], eb[k], dim=1) for k in ea]).mean())
 
 
+def fx_encoder_similarity(a: torch.Tensor, b: torch.Tensor, fx_model, sr: int) -> float:
+    """cosine_similarity of the FX-Encoder embeddings, scored like style_distance.  The reference's eval_pst.py imports
+    load_fx_encoder_model / get_fx_encoder_embeds (24-25) without listing the encoder among its metrics: this entry is an
+    extension.  Each side is embedded on its own, so each is normalised by its own peak."""
+    from st_ito.utils import get_fx_encoder_embeds
+
+    ea, eb = get_fx_encoder_embeds(a, fx_model, sr)["stereo"], get_fx_encoder_embeds(b, fx_model, sr)["stereo"]
+    return float(torch.cosine_similarity(ea, eb, dim=1).mean())
+
+
 # --methods choice -> the reference's result key (eval_pst.py:945-991)
 METHODS = OrderedDict([("input", "input"), ("random", "random"), ("rule-based", "rule-based"), ("style-es", "style-es (param-panns)")])
 DEFAULT_METHODS = ("input", "style-es")
@@ -89,9 +99,10 @@ DEFAULT_METHODS = ("input", "style-es")
 
 def run_pst_benchmark(pairs, plugins, model, out_dir: str, max_iters: int = 32, popsize: int = 128, sigma0: float = 0.33,
                       random_crop: bool = True, seed: int = None, batched: bool = False, tag: str = "pb",
-                      methods=DEFAULT_METHODS):
+                      methods=DEFAULT_METHODS, fx_model=None):
     """pairs: list of (name, input (chs, n), input_sr, target (chs, n), target_sr).  Returns the results dict
-    the reference dumps to JSON: per method, per metric, one value per example (+ time_elapsed).
+    the reference dumps to JSON: per method, per metric, one value per example (+ time_elapsed).  fx_model: an FXencoder, or
+    None; with one every result is also scored by fx_encoder_similarity under "fx_encoder".
 
     methods: any of "input", "random", "rule-based", "style-es" (results in that order, under the reference's keys).  Every
     method gets clones of the prepared pair; its time_elapsed is the wall time of its call, like the reference's (757-763;
@@ -111,7 +122,7 @@ def run_pst_benchmark(pairs, plugins, model, out_dir: str, max_iters: int = 32, 
     plugins, _, _ = load_plugins(plugins)
     sr = 48000
     prepared = [(name,) + prepare_pair(x, xsr, t, tsr) for name, x, xsr, t, tsr in pairs]
-    results = {METHODS[m]: {"time_elapsed": [], "style_features": []} for m in methods}
+    results = {METHODS[m]: {"time_elapsed": [], "style_features": [], **({} if fx_model is None else {"fx_encoder": []})} for m in methods}
 
     def timed(fn, *a, **k):
         t0 = time.time()
@@ -150,6 +161,8 @@ def run_pst_benchmark(pairs, plugins, model, out_dir: str, max_iters: int = 32, 
             method = METHODS[m]
             results[method]["time_elapsed"].append(elapsed)
             results[method]["style_features"].append(style_distance(out_audio[None], tgt, model, sr))
+            if fx_model is not None:
+                results[method]["fx_encoder"].append(fx_encoder_similarity(out_audio[None], tgt, fx_model, sr))
             stem = f"{idx:02d}_{method.split(' ')[0]}_{tag}"
             if params is not None:
                 with open(os.path.join(out_dir, stem + ".json"), "w") as f:
@@ -161,6 +174,8 @@ def run_pst_benchmark(pairs, plugins, model, out_dir: str, max_iters: int = 32, 
     print()
     for method, res in results.items():
         print(f"{method}:\n\tstyle_features: {np.mean(res['style_features'])}")
+        if fx_model is not None:
+            print(f"\tfx_encoder: {np.mean(res['fx_encoder'])}")
     with open(os.path.join(out_dir, f"results_{datetime.now().strftime('%Y-%m-%d_%H-%M-%S')}.json"), "w") as f:
         json.dump(results, f, indent=2)
     return results
@@ -200,12 +215,18 @@ def main(argv=None):
     ap.add_argument("--methods", nargs="+", default=list(DEFAULT_METHODS), choices=list(METHODS) + ["deepafx-st"],
                     help="methods to run (deepafx-st: not built, raises)")
     ap.add_argument("--output-dir", default=os.path.join("output", "pst"))
+    ap.add_argument("--metrics", nargs="*", default=[], choices=["fx_encoder"],
+                    help="further scores of every result next to style_features; fx_encoder: cosine similarity of FX-Encoder embeddings")
+    ap.add_argument("--fx-ckpt", default=None, help="FX-Encoder checkpoint for --metrics fx_encoder; omitted: seeded random weights")
     a = ap.parse_args(argv)
 
     from st_ito.audio_io import load_wav
-    from st_ito.utils import load_param_model, make_synthetic_param_model
+    from st_ito.utils import load_fx_encoder_model, load_param_model, make_synthetic_fx_encoder, make_synthetic_param_model
 
     model = load_param_model(a.ckpt, use_gpu=True) if a.ckpt else make_synthetic_param_model(0)
+    fx_model = None
+    if "fx_encoder" in a.metrics:
+        fx_model = load_fx_encoder_model(use_gpu=True, ckpt_path=a.fx_ckpt) if a.fx_ckpt else make_synthetic_fx_encoder(0)
     plugins = get_plugins(a.chain)
     if a.synthetic:
         pairs = synthetic_pairs(a.synthetic, a.seconds, plugins)
@@ -219,7 +240,7 @@ def main(argv=None):
     else:
         ap.error("give --pairs or --synthetic N")
     return run_pst_benchmark(pairs, plugins, model, os.path.join(a.output_dir, a.chain), a.max_iters, a.popsize,
-                             seed=a.seed, batched=a.batched, tag=a.chain, methods=a.methods)
+                             seed=a.seed, batched=a.batched, tag=a.chain, methods=a.methods, fx_model=fx_model)
 
 
 if __name__ == "__main__":

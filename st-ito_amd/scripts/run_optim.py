@@ -46,12 +46,14 @@ def build_parser():
     parser.add_argument("--effect-type", type=str, default="vst", choices=["vst", "basic"])
     parser.add_argument("--algorithm", type=str, default="es", choices=["es", "autodiff"])
     parser.add_argument("--dropout", type=float, default=0.0)
-    parser.add_argument("--metric", type=str, default="param", choices=["param", "clap"])
+    parser.add_argument("--metric", type=str, default="param", choices=["param", "clap", "fx_encoder"],
+                        help="param: AFx-Rep (the reference's default); fx_encoder: FX-Encoder embeddings (--ckpt: FXencoder_ps.pt, "
+                             "or --synthetic); clap: not built")
     # extensions
     parser.add_argument("--seed", type=int, default=None)
     parser.add_argument("--chain", type=str, default=None, choices=sorted(effects.BASIC_CHAINS))
     parser.add_argument("--ckpt", type=str, default=None)
-    parser.add_argument("--synthetic", action="store_true", help="seeded random AFx-Rep weights (no checkpoint)")
+    parser.add_argument("--synthetic", action="store_true", help="seeded random weights of the --metric model (no checkpoint)")
     parser.add_argument("--no-early-stop", action="store_true")
     parser.add_argument("--no-find-w0", action="store_true")
     parser.add_argument("--output-dir", type=str, default="output/optim")
@@ -79,7 +81,7 @@ def main(argv=None):
     sample_rate = 48000
     if args.algorithm != "es":
         raise NotImplementedError("--algorithm autodiff (run_optim.py:237-297) is outside this build: ES path only")
-    if args.metric != "param":
+    if args.metric == "clap":
         raise NotImplementedError("--metric clap needs laion_clap + downloaded weights; only the AFx-Rep metric is built")
     if args.device_es and args.staged:
         raise ValueError("--device-es drives run_es only: it cannot be combined with --staged")
@@ -129,6 +131,11 @@ def main(argv=None):
 
     if args.objective in AUDIO_OBJECTIVES:
         model, embed_func = None, None  # the distance is taken on the audio: no checkpoint
+    elif args.metric == "fx_encoder":   # the generic-metric path of run_es: render, one GPU tensor to the embed function
+        from st_ito.utils import get_fx_encoder_embeds, load_fx_encoder_model, make_synthetic_fx_encoder
+        ckpt = {} if args.ckpt is None else {"ckpt_path": args.ckpt}
+        model = make_synthetic_fx_encoder(seed=0) if args.synthetic else load_fx_encoder_model(use_gpu=args.use_gpu, **ckpt)
+        embed_func = get_fx_encoder_embeds
     else:
         model = make_synthetic_param_model(seed=0) if args.synthetic else load_param_model(ckpt_path=args.ckpt, use_gpu=args.use_gpu)
         embed_func = get_param_embeds

@@ -68,6 +68,17 @@ class MelBank(Structure):
     ]
 
 
+class FxencLayer(Structure):
+    _fields_ = [
+        ("cin", c_int32), ("cout", c_int32), ("kernel", c_int32), ("stride", c_int32), ("dilation", c_int32), ("residual", c_int32),
+        ("w_packed_dev", c_void_p), ("scale_dev", c_void_p), ("shift_dev", c_void_p),
+    ]
+
+
+class FxencModel(Structure):
+    _fields_ = [("n_layers", c_int32), ("reserved", c_int32), ("layers", POINTER(FxencLayer))]
+
+
 class StitoError(RuntimeError):
     pass
 
@@ -200,6 +211,15 @@ SIGNATURES = {
     "stito_cmaes_import": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int64), POINTER(c_double), c_void_p]),
     "stito_cmaes_status": (c_int, [c_void_p, POINTER(c_int64), c_void_p]),
     "stito_cmaes_normals": (c_int, [c_uint64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    # the FX-Encoder (ABI 10.11)
+    "stito_fxenc_out_len": (c_int64, [c_int64, c_int]),
+    "stito_fxenc_tile_m": (c_int, [c_int, c_int, c_int, c_int]),
+    "stito_fxenc_tile_k": (c_int, []),
+    "stito_fxenc_packed_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "stito_fxenc_conv1d": (c_int, [POINTER(FxencLayer), c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "stito_fxenc_pool": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "stito_fxenc_workspace_bytes": (c_size_t, [POINTER(FxencModel), c_int, c_int64]),
+    "stito_fxenc_forward": (c_int, [POINTER(FxencModel), c_void_p, c_int, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 

@@ -1,5 +1,6 @@
 """Loader / embedding-function pair of the AFx-Rep metric: the reference's
-st_ito/utils.py:444-551 (`get_param_embeds`, `load_param_model`) plus `apply_fade_in` (31-43).
+st_ito/utils.py:444-551 (`get_param_embeds`, `load_param_model`) plus `apply_fade_in` (31-43), and of its
+FX-Encoder baseline (554-608: `get_fx_encoder_embeds`, `load_fx_encoder_model`).
 The other metrics of the reference's utils.py (CLAP, BEATs, wav2vec2, ...) are outside this
 build's scope."""
 from __future__ import annotations
@@ -184,6 +185,85 @@ def make_synthetic_param_model(seed: int = 0, input_norm: str = "minmax", embed_
     if torch.cuda.is_available():
         model.cuda()
     model.reference_device = "cuda" if torch.cuda.is_available() else "cpu"  # as load_param_model(use_gpu=...) records it (get_param_embeds)
+    return model
+
+
+# ------------------- FX-Encoder (reference utils.py:554-608) ---------------- #
+def load_fx_encoder_model(use_gpu: bool = False, ckpt_path: str = "checkpoints/FXencoder_ps.pt"):
+    """reference utils.py:582-608: the default FXencoder with the weights of checkpoint["model"] (a leading `module.` stripped).
+    Nothing is fetched: a missing file is a FileNotFoundError.  The forward only exists on the GPU, so the model is moved to
+    the current HIP device whenever one is visible (embeddings come back on the input's device, as in the reference)."""
+    from .models.fx_encoder import FXencoder
+
+    if not os.path.isfile(ckpt_path):
+        raise FileNotFoundError(
+            f"{ckpt_path} not found.  Put the FX-Encoder checkpoint (FXencoder_ps.pt of jhtonyKoo/music_mixing_style_transfer) "
+            "there (no network access here), or use st_ito.utils.make_synthetic_fx_encoder() for benchmarking.")
+    model = FXencoder()
+    model.load_state_dict(_load_checkpoint(ckpt_path)["model"])
+    model.embed_dim = 2048
+    model.eval()
+    if use_gpu or torch.cuda.is_available():
+        model.cuda()
+    return model
+
+
+def get_fx_encoder_embeds(x: torch.Tensor, model, sample_rate: float, peak: str = "batch", **kwargs):
+    """reference utils.py:554-579.  x (bs, chs, seq_len), chs 1 or 2 -> {"stereo": (bs, embed_dim)} with x's device and dtype:
+    resampled to 44.1 kHz (stito_resample_sinc), peak-normalised, a mono input repeated to two channels, then the encoder.
+
+    peak="batch" (the default) is the reference's normalisation: ONE scalar, x.abs().max().clamp(1e-8), over the whole tensor,
+    the batch included.  An item's embedding then depends on the loudest item of its batch, so the fitness of a population
+    that is evaluated in shards (max_candidates_per_pass, several ranks) depends on the sharding; that is the reference's
+    behaviour and is kept.  peak="item" divides every item by its own peak: an item's embedding is then the same bits alone
+    and in any batch.  Unlike the reference, which at 44.1 kHz divides the caller's tensor in place, x is never modified."""
+    if x.dim() != 3:
+        raise ValueError("expected (bs, chs, seq_len)")
+    if peak not in ("batch", "item"):
+        raise ValueError(f'peak must be "batch" or "item", not {peak!r}')
+    from .models.fx_encoder import FXencoder
+
+    if not isinstance(model, FXencoder):
+        raise TypeError("get_fx_encoder_embeds (MI355X build) needs an st_ito.models.fx_encoder.FXencoder")
+    _hip.require_gpu()
+    xin = x.detach().to(model._device(), torch.float32)
+    if sample_rate != 44100:
+        from .audio_io import resample
+
+        xin = resample(xin.contiguous(), int(sample_rate), 44100)
+    if peak == "batch":
+        xin = xin / xin.abs().max().clamp(1e-8)
+    else:
+        xin = xin / xin.abs().amax(dim=(1, 2), keepdim=True).clamp(1e-8)
+    if xin.shape[1] == 1:
+        xin = xin.repeat(1, 2, 1)
+    embed = model(xin)
+    return {"stereo": embed.to(x.device).type_as(x)}
+
+
+def make_synthetic_fx_encoder(seed: int = 0, channels=None, kernels=None, strides=None):
+    """Seeded random FXencoder (the default configuration unless told otherwise) for tests, benchmarks and --synthetic when the
+    checkpoint is unavailable: unit-gain weights, and batch-norm statistics that exercise the fold -- gamma negative for about
+    one channel in six, running variance between 0.25 and 1.75."""
+    from .models.fx_encoder import FXencoder
+
+    model = FXencoder(channels=channels, kernels=kernels, strides=strides)
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for _, ly in model.layers():
+            conv, bn = ly.conv1d.conv1d, ly.conv1d.batch_norm
+            n = ly.cout
+            # unit gain: a block adds its input back, He's factor 2 would double the power twelve times over
+            conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (1.0 / (ly.cin * ly.kernel)) ** 0.5)
+            conv.bias.copy_(0.1 * torch.randn(n, generator=g))
+            gamma = 0.75 + 0.5 * torch.rand(n, generator=g)
+            bn.weight.copy_(torch.where(torch.rand(n, generator=g) < 1.0 / 6.0, -gamma, gamma))
+            bn.bias.copy_(0.2 + 0.1 * torch.randn(n, generator=g))
+            bn.running_mean.copy_(0.1 * torch.randn(n, generator=g))
+            bn.running_var.copy_(0.25 + 1.5 * torch.rand(n, generator=g))
+    model.eval()
+    if torch.cuda.is_available():
+        model.cuda()
     return model
 
 
