@@ -39,11 +39,11 @@
 // zero padding -- on the normalised (and, under SD, combined) row, and everything behind the loader sees p: the STFT's reflect
 // padding reflects the FILTERED row.  The reflected sample indices of a tile's span form one contiguous run [s_min, s_max] of the
 // row, so the workgroup stages the raw run [s_min - c, s_max + c] where the span will lie, every thread filters runs of four
-// consecutive outputs from a sliding register window (16 fmas per four new samples from LDS; the taps, the same for every lane,
-// come through scalar loads; the chain of each output is fmaf in tap order from 0.0f), keeps them in registers across a barrier,
+// consecutive outputs from a sliding register window (ad_fir_run of audio_distance.h), keeps them in registers across a barrier,
 // writes them over the raw run, and a second register pass lays the span out through the reflection.  LDS grows by the filter's
-// reach (256 floats), not by a second span.
-#include "common.h"
+// reach (256 floats), not by a second span.  audio_distance.h holds what this file shares with waveform.hip: the slot rule, the folded
+// peak, that FIR run, the tile tree and the host checks of a loss call and of the taps.
+#include "audio_distance.h"
 
 #include <type_traits>
 
@@ -52,10 +52,8 @@ namespace stito {
 static constexpr int MR_THREADS = 256, MR_WAVES = MR_THREADS / 64;
 static constexpr int MR_MAX_RES = 8;
 static constexpr int MR_MAX_CH = 8;  // the final sum gives one lane of a wave to every (resolution, channel)
-// The prefilter: up to 255 taps, taken in blocks of four, so the raw run reaches MR_PF_REACH samples past its last whole float4; a
-// thread filters MR_PF_GROUPS runs of four outputs and holds them in registers, so a prefiltered tile's span has at most
-// MR_PF_MAX_SPAN samples (the plan picks F accordingly).
-static constexpr int MR_PF_MAX_TAPS = 255, MR_PF_REACH = 256;
+// The prefilter (up to AD_MAX_TAPS taps, the raw run reaches AD_TAP_REACH samples past its last whole float4): a thread filters
+// MR_PF_GROUPS runs of four outputs and holds them in registers, so a prefiltered tile's span has at most MR_PF_MAX_SPAN samples.
 static constexpr int MR_PF_GROUPS = 8;
 static constexpr int MR_PF_MAX_SPAN = 4 * MR_PF_GROUPS * MR_THREADS;
 
@@ -79,7 +77,7 @@ static size_t mr_lds_bytes(int N, int hop, int F, bool pre = false) {
     const size_t plain = (size_t)2 * MR_THREADS * 8 + (size_t)MR_WAVES * (N / 2) * 8 + (size_t)(N / 2) * 8 + (size_t)N * 4 +
                          ((size_t)(F - 1) * hop + N) * 4;
     // prefiltered: the span rounded up to whole float4 and the filter's reach behind the raw run (whole tap blocks)
-    return pre ? plain + (size_t)(4 + MR_PF_REACH) * 4 : plain;
+    return pre ? plain + (size_t)(4 + AD_TAP_REACH) * 4 : plain;
 }
 
 // n_bins: 0 for the linear table (a row of a frame is its n_fft / 2 + 1 bins), else the bands of the mel table.  The LDS, the
@@ -281,24 +279,12 @@ __device__ __forceinline__ float mr_mel_band(const MrDevMel &d, const float2 *bu
     return acc;
 }
 
-// Table target of candidate `cand`: population k = cand / per_target reads target slots[k], or target k when there is no slot
-// list (the identity map: stito_mrstft_loss).  -1 for a slot that names no target of the table.
-__device__ __forceinline__ int mr_target_of(int64_t cand, int per_target, const int32_t *__restrict__ slots, int n_targets) {
-    const int k = (int)(cand / per_target);
-    const int t = slots != nullptr ? slots[k] : k;
-    return (t >= 0 && t < n_targets) ? t : -1;
-}
-
-// The prefiltered loader.  span: room for the tile's largest span rounded up to whole float4 and MR_PF_REACH floats behind it
+// The prefiltered loader.  span: room for the tile's largest span rounded up to whole float4 and AD_TAP_REACH floats behind it
 // (mr_lds_bytes).  On return span[0 .. span_len) holds the reflected FILTERED samples; the caller's barrier
 // publishes them.  x, r1, row: as in the plain loader (SD: x is the item's channel 0 and the row's parity picks sum or difference).
 template <bool SD>
 __device__ __forceinline__ void mr_prefiltered_span(const float *__restrict__ x, int64_t n, float r1, int64_t row, const float *__restrict__ taps,
                                                     int n_taps, float *span, int64_t s0, int span_len, int tid) {
-    // the taps are the same for every lane and nobody writes them: read through the constant address space they come as scalar
-    // loads into SGPRs and leave the LDS pipe to the samples
-    typedef const __attribute__((address_space(4))) float *ctaps_t;
-    ctaps_t ctaps = (ctaps_t)(uintptr_t)taps;
     // the samples the span reflects to: [max(a, 0), min(b, n - 1)], 1 .. -a before the row's start, 2 (n - 1) - b .. n - 2 behind its end
     const int c = n_taps >> 1;
     const int64_t a = s0, b = s0 + span_len - 1;
@@ -324,41 +310,18 @@ __device__ __forceinline__ void mr_prefiltered_span(const float *__restrict__ x,
         span[i] = v;
     }
     __syncthreads();
-    // outputs 4 g .. 4 g + 3 of group g from the window raw[4 g + 4 kb .. + 7]; every output's chain runs k = 0 .. n_taps - 1
-    float out[MR_PF_GROUPS][4];
-    const int kb_full = n_taps >> 2, tail = n_taps & 3;           // n_taps is odd: 1 or 3 taps behind the whole blocks
+    // outputs 4 g .. 4 g + 3 of group g; every output's chain runs k = 0 .. n_taps - 1
+    float4 out[MR_PF_GROUPS];
 #pragma unroll
     for (int gi = 0; gi < MR_PF_GROUPS; ++gi) {
         const int g = tid + gi * MR_THREADS;
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-        if (4 * g < run_len) {
-            const float4 *rp = (const float4 *)span + g;
-            float4 lo = rp[0];
-            for (int kb = 0; kb < kb_full; ++kb) {
-                const float4 hi = rp[kb + 1];
-                const float4 t = make_float4(ctaps[4 * kb], ctaps[4 * kb + 1], ctaps[4 * kb + 2], ctaps[4 * kb + 3]);
-                a0 = fmaf(t.x, lo.x, a0); a1 = fmaf(t.x, lo.y, a1); a2 = fmaf(t.x, lo.z, a2); a3 = fmaf(t.x, lo.w, a3);
-                a0 = fmaf(t.y, lo.y, a0); a1 = fmaf(t.y, lo.z, a1); a2 = fmaf(t.y, lo.w, a2); a3 = fmaf(t.y, hi.x, a3);
-                a0 = fmaf(t.z, lo.z, a0); a1 = fmaf(t.z, lo.w, a1); a2 = fmaf(t.z, hi.x, a2); a3 = fmaf(t.z, hi.y, a3);
-                a0 = fmaf(t.w, lo.w, a0); a1 = fmaf(t.w, hi.x, a1); a2 = fmaf(t.w, hi.y, a2); a3 = fmaf(t.w, hi.z, a3);
-                lo = hi;
-            }
-            const float4 hi = rp[kb_full + 1];
-            float4 t = make_float4(ctaps[4 * kb_full], 0.0f, 0.0f, 0.0f);                  // no read behind the last tap
-            a0 = fmaf(t.x, lo.x, a0); a1 = fmaf(t.x, lo.y, a1); a2 = fmaf(t.x, lo.z, a2); a3 = fmaf(t.x, lo.w, a3);
-            if (tail == 3) {
-                t.y = ctaps[4 * kb_full + 1]; t.z = ctaps[4 * kb_full + 2];
-                a0 = fmaf(t.y, lo.y, a0); a1 = fmaf(t.y, lo.z, a1); a2 = fmaf(t.y, lo.w, a2); a3 = fmaf(t.y, hi.x, a3);
-                a0 = fmaf(t.z, lo.z, a0); a1 = fmaf(t.z, lo.w, a1); a2 = fmaf(t.z, hi.x, a2); a3 = fmaf(t.z, hi.y, a3);
-            }
-        }
-        out[gi][0] = a0; out[gi][1] = a1; out[gi][2] = a2; out[gi][3] = a3;
+        out[gi] = 4 * g < run_len ? ad_fir_run(span, g, taps, n_taps) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
     __syncthreads();  // the raw run has been read: p goes over it, p[s_min + o] at span[o]
 #pragma unroll
     for (int gi = 0; gi < MR_PF_GROUPS; ++gi) {
         const int g = tid + gi * MR_THREADS;
-        if (4 * g < run_len) ((float4 *)span)[g] = make_float4(out[gi][0], out[gi][1], out[gi][2], out[gi][3]);
+        if (4 * g < run_len) ((float4 *)span)[g] = out[gi];
     }
     __syncthreads();
     // the span through the reflection (no edge repeat), again by way of registers: span index i = padded index s0 + i
@@ -383,7 +346,7 @@ __device__ __forceinline__ void mr_prefiltered_span(const float *__restrict__ x,
 }
 
 // TARGET: audio = y (rows, n); writes the magnitudes and the tile's sum |Y|^2 (K = 1 partial).
-// else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row mr_target_of(cand) * C + ch;
+// else:   audio = candidates (pop, C, n); row = cand * C + ch is compared with table row ad_target_of(cand) * C + ch;
 //         the tile's sum (|Y| - |X|)^2 and sum |ln(|X| / |Y|)| (K = 2 partials).  A candidate whose slot names no target
 //         reads nothing from the table and writes no partial: k_mrstft_final gives it NaN.
 // SD:     C = 2 and audio = (items, 2, n) on both sides; row 2 item + 0 is the item's L + R, row 2 item + 1 its L - R.
@@ -395,8 +358,8 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrArgOf<MEL, PRE> d, cons
                                                       int n_targets) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int N = d.N, N2 = d.N2;
-    double *red = (double *)smem_raw;                          // [2][MR_THREADS]
-    float2 *bufs = (float2 *)(red + 2 * MR_THREADS);           // [MR_WAVES][N2]
+    double (*red)[MR_THREADS] = (double (*)[MR_THREADS])smem_raw;   // [2][MR_THREADS]
+    float2 *bufs = (float2 *)(red + 2);                             // [MR_WAVES][N2]
     float2 *tw_s = bufs + MR_WAVES * N2;                       // [N2]
     float *win_s = (float *)(tw_s + N2);                       // [N]
     float *span = win_s + N;                                   // [(F - 1) hop + N]
@@ -411,9 +374,9 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrArgOf<MEL, PRE> d, cons
     int64_t trow = row;
     if (!TARGET) {
         const int64_t cand = row / C;
-        const int t = mr_target_of(cand, per_target, slots, n_targets);
+        const int t = ad_target_of(cand, per_target, slots, n_targets);
         if (t < 0) return;  // the whole workgroup (one row, one candidate), before it loads anything
-        if (peaks != nullptr && norm_passes > 0) r1 = 1.0f / fmaxf(peaks[cand], 1e-8f);  // x * (1 / d), as stito_logmel
+        r1 = ad_peak_scale(peaks, norm_passes, cand);
         trow = (int64_t)t * C + (row - cand * C);
     }
     const float *x = audio + (SD ? (row & ~(int64_t)1) : row) * d.n;  // SD: the item's channel 0; channel 1 lies behind it
@@ -463,22 +426,13 @@ __global__ __launch_bounds__(MR_THREADS) void k_mrstft(MrArgOf<MEL, PRE> d, cons
         MR_WAVE_SYNC()  // the spectrum has been read before the next frame is packed over it
     }
 
-    // the tile's sums: a fixed tree over the threads
-    red[tid] = acc0;
-    red[MR_THREADS + tid] = acc1;
-    __syncthreads();
-    for (int s = MR_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[tid] += red[tid + s];
-            red[MR_THREADS + tid] += red[MR_THREADS + tid + s];
-        }
-        __syncthreads();
-    }
+    const double acc[2] = {acc0, acc1};
+    ad_tile_tree<2, MR_THREADS>(red, acc, tid);
     if (tid == 0) {
         constexpr int K = TARGET ? 1 : 2;
         double *out = d.partial + (row * d.tiles_total + tile) * K;
-        out[0] = red[0];
-        if (!TARGET) out[1] = red[MR_THREADS];
+        out[0] = red[0][0];
+        if (!TARGET) out[1] = red[1][0];
     }
 }
 
@@ -521,7 +475,7 @@ __global__ __launch_bounds__(64) void k_mrstft_final(MrSum s, const double *__re
                                                      float *__restrict__ loss) {
     __shared__ double term[64];
     const int cand = blockIdx.x, lane = threadIdx.x;
-    const int tgt = mr_target_of(cand, per_target, slots, n_targets);
+    const int tgt = ad_target_of(cand, per_target, slots, n_targets);
     if (tgt < 0) {  // the whole wave: no partial was written for this candidate and none is read
         if (lane == 0) loss[cand] = __builtin_nanf("");
         return;
@@ -653,9 +607,9 @@ static int mr_sd_channels(const char *who, int channels) {
 // The one launch path of the table.  SD: y_dev is (rows / 2, 2, n) and row 2 t + 0 / 1 of the table is target t's L + R / L - R.
 // MEL: the rows of the table are band sums through `bank`, which has been checked.
 // PRE: the rows are filtered with the n_taps taps at taps_dev, which have been checked.
-template <bool SD, bool MEL = false, bool PRE = false>
+template <bool SD, bool MEL, bool PRE>
 static int mr_target(const char *who, const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
-                     void *stream, const stito_mel_bank *bank = nullptr, const float *taps_dev = nullptr, int n_taps = 0) {
+                     void *stream, const stito_mel_bank *bank, const float *taps_dev, int n_taps) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
     STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0, PRE));
@@ -681,43 +635,24 @@ static int mr_target(const char *who, const int *res, int n_res, const float *y_
     return STITO_OK;
 }
 
-extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
-                                   void *stream) {
-    return mr_target<false>("stito_mrstft_target", res, n_res, y_dev, rows, n_samples, table_dev, stream);
-}
-
-extern "C" int stito_mrstft_target_sd(const int *res, int n_res, const float *y_dev, int n_targets, int channels, int64_t n_samples,
-                                      float *table_dev, void *stream) {
-    STITO_TRY(mr_sd_channels("stito_mrstft_target_sd", channels));
-    STITO_REQUIRE(n_targets >= 1 && n_targets < (1 << 30), STITO_E_INVALID, "stito_mrstft_target_sd: %d targets", n_targets);
-    return mr_target<true>("stito_mrstft_target_sd", res, n_res, y_dev, 2 * n_targets, n_samples, table_dev, stream);
-}
-
 // The one launch path of the loss: populations of pop / n_slots candidates, population k against target target_slot[k] of the
 // table's n_targets, or against target k when there is no slot list (then n_slots == n_targets).
-template <bool SD, bool MEL = false, bool PRE = false>
+template <bool SD, bool MEL, bool PRE>
 static int mr_loss(const char *who, const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                    const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
                    int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
-                   const stito_mel_bank *bank = nullptr, const float *taps_dev = nullptr, int n_taps = 0) {
+                   const stito_mel_bank *bank, const float *taps_dev, int n_taps) {
     hipStream_t st = (hipStream_t)stream;
     MrPlan p;
     STITO_TRY(mr_plan(res, n_res, n_samples, p, MEL ? bank->n_bins : 0, PRE));
     STITO_TRY(mr_device_fits(p));
-    STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "%s: pop %d, n_targets %d", who, pop, n_targets);
-    STITO_REQUIRE(n_slots >= 1, STITO_E_INVALID, "%s: %d target slots", who, n_slots);
-    STITO_REQUIRE(pop % n_slots == 0, STITO_E_INVALID, "%s: population %d is not a multiple of the number of targets %d", who, pop, n_slots);
-    if (SD) STITO_TRY(mr_sd_channels(who, channels));
-    STITO_REQUIRE(channels >= 1 && channels <= MR_MAX_CH && n_res * channels <= 64, STITO_E_INVALID, "Invalid number of channels: %d", channels);
-    STITO_REQUIRE(norm_passes == 0 || norm_passes == 1, STITO_E_INVALID, "%s: norm_passes %d must be 0 or 1", who, norm_passes);
-    STITO_REQUIRE(norm_passes == 0 || peaks_dev != nullptr, STITO_E_INVALID, "%s: norm_passes 1 needs the peaks", who);
-    STITO_REQUIRE(audio_dev != nullptr && table_dev != nullptr && loss_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);
-    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "%s: the table must be 16-byte aligned", who);
+    STITO_TRY(ad_loss_args_check(who, pop, n_targets, n_slots, [&] {
+        if (SD) STITO_TRY(mr_sd_channels(who, channels));
+        STITO_REQUIRE(channels >= 1 && channels <= MR_MAX_CH && n_res * channels <= 64, STITO_E_INVALID, "Invalid number of channels: %d", channels);
+        return STITO_OK;
+    }, norm_passes, peaks_dev, audio_dev, table_dev, loss_dev));
     const int64_t rows = (int64_t)pop * channels, trows = (int64_t)n_targets * channels;
-    const size_t need = (size_t)rows * p.tiles_total * 2 * sizeof(double);
-    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= need, STITO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-                  workspace_bytes, need);
-    STITO_REQUIRE(((uintptr_t)workspace_dev & 7) == 0, STITO_E_INVALID, "%s: the workspace must be 8-byte aligned", who);
+    STITO_TRY(ad_workspace_check(who, workspace_dev, workspace_bytes, (size_t)rows * p.tiles_total * 2 * sizeof(double)));
     for (int i = 0; i < p.n_res; ++i)
         STITO_REQUIRE(rows * p.tiles[i] < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "%s: too many tiles", who);
     double *partial = (double *)workspace_dev;
@@ -735,38 +670,95 @@ static int mr_loss(const char *who, const int *res, int n_res, const float *audi
     return STITO_OK;
 }
 
+// The prefiltered calls' own arguments (ABI 10.9): kind -- 0 the L/R distance, 1 sum / difference, 2 mel (with its bank) -- and the
+// taps.  The table does not record the taps: table and loss calls take the same.
+static int mr_pf_check(const char *who, int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res) {
+    STITO_REQUIRE(kind >= 0 && kind <= 2, STITO_E_INVALID, "%s: kind %d is none of 0 (L/R), 1 (sum / difference), 2 (mel)", who, kind);
+    STITO_TRY(ad_taps_check(who, taps_dev, n_taps, false));
+    if (kind == 2) return mr_bank_check(who, bank, res, n_res);
+    STITO_REQUIRE(bank == nullptr, STITO_E_INVALID, "%s: kind %d takes no bank", who, kind);
+    return STITO_OK;
+}
+
+// (kind, prefiltered) -> the <SD, MEL, PRE> instantiation, stated once: f(sd, mel, pre) with three std::bool_constant.
+template <class F>
+static auto mr_dispatch(int kind, bool pre, F &&f) {
+    using Y = std::true_type; using N = std::false_type;
+    switch (kind) {
+        case 1: return pre ? f(Y{}, N{}, Y{}) : f(Y{}, N{}, N{});
+        case 2: return pre ? f(N{}, Y{}, Y{}) : f(N{}, Y{}, N{});
+        default: return pre ? f(N{}, N{}, Y{}) : f(N{}, N{}, N{});
+    }
+}
+
+// What every table export ends in, its own arguments checked: the table of `rows` rows of that kind, prefiltered or not.
+static int mr_target_call(const char *who, int kind, bool pre, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res,
+                          int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev, void *stream) {
+    return mr_dispatch(kind, pre, [&](auto sd, auto mel, auto pf) {
+        return mr_target<sd.value, mel.value, pf.value>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, bank, taps_dev, n_taps);
+    });
+}
+
+// What every loss export is: the checks of its own arguments in the order they have always been made -- a prefiltered call's kind,
+// taps and (sum / difference) 2 channels, a mel call's bank, the slot list where the call takes one -- and mr_loss of that kind.
+static int mr_loss_call(const char *who, int kind, bool pre, bool slots, const stito_mel_bank *bank, const float *taps_dev, int n_taps,
+                        const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev,
+                        int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples, float *loss_dev,
+                        void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (pre) STITO_TRY(mr_pf_check(who, kind, bank, taps_dev, n_taps, res, n_res));
+    if (pre && kind == 1) STITO_TRY(mr_sd_channels(who, channels));
+    if (!pre && kind == 2) STITO_TRY(mr_bank_check(who, bank, res, n_res));
+    if (slots) STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "%s: null target_slot_dev", who);
+    return mr_dispatch(kind, pre, [&](auto sd, auto mel, auto pf) {
+        return mr_loss<sd.value, mel.value, pf.value>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
+                                                      slots ? target_slot_dev : nullptr, slots ? n_slots : n_targets, pop, channels, n_samples,
+                                                      loss_dev, workspace_dev, workspace_bytes, stream, bank, taps_dev, n_taps);
+    });
+}
+
+extern "C" int stito_mrstft_target(const int *res, int n_res, const float *y_dev, int rows, int64_t n_samples, float *table_dev,
+                                   void *stream) {
+    return mr_target_call("stito_mrstft_target", 0, false, nullptr, nullptr, 0, res, n_res, y_dev, rows, n_samples, table_dev, stream);
+}
+
 extern "C" int stito_mrstft_loss(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                                  const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
                                  void *workspace_dev, size_t workspace_bytes, void *stream) {
-    return mr_loss<false>("stito_mrstft_loss", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets,
-                          pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss_call("stito_mrstft_loss", 0, false, false, nullptr, nullptr, 0, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev,
+                        n_targets, nullptr, 0, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int stito_mrstft_loss_slots(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                                        const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
                                        int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
                                        void *stream) {
-    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots: null target_slot_dev");
-    return mr_loss<false>("stito_mrstft_loss_slots", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
-                          target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss_call("stito_mrstft_loss_slots", 0, false, true, nullptr, nullptr, 0, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev,
+                        n_targets, target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 // The sum / difference variants (ABI 10.7): the same calls on the 2-channel signal [L + R, L - R] of every item, against a table
 // that stito_mrstft_target_sd wrote.
+extern "C" int stito_mrstft_target_sd(const int *res, int n_res, const float *y_dev, int n_targets, int channels, int64_t n_samples,
+                                      float *table_dev, void *stream) {
+    const char *who = "stito_mrstft_target_sd";
+    STITO_TRY(mr_sd_channels(who, channels));
+    STITO_REQUIRE(n_targets >= 1 && n_targets < (1 << 30), STITO_E_INVALID, "%s: %d targets", who, n_targets);
+    return mr_target_call(who, 1, false, nullptr, nullptr, 0, res, n_res, y_dev, 2 * n_targets, n_samples, table_dev, stream);
+}
+
 extern "C" int stito_mrstft_loss_sd(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                                     const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples, float *loss_dev,
                                     void *workspace_dev, size_t workspace_bytes, void *stream) {
-    return mr_loss<true>("stito_mrstft_loss_sd", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets,
-                         pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss_call("stito_mrstft_loss_sd", 1, false, false, nullptr, nullptr, 0, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev,
+                        n_targets, nullptr, 0, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int stito_mrstft_loss_slots_sd(const int *res, int n_res, const float *audio_dev, const float *peaks_dev, int norm_passes,
                                           const float *table_dev, int n_targets, const int32_t *target_slot_dev, int n_slots, int pop,
                                           int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
                                           void *stream) {
-    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots_sd: null target_slot_dev");
-    return mr_loss<true>("stito_mrstft_loss_slots_sd", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
-                         target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss_call("stito_mrstft_loss_slots_sd", 1, false, true, nullptr, nullptr, 0, res, n_res, audio_dev, peaks_dev, norm_passes,
+                        table_dev, n_targets, target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 // The mel variants (ABI 10.8): the L/R calls with band sums M = F |X| in the place of the magnitudes, F the caller's bank.
@@ -779,41 +771,27 @@ extern "C" int64_t stito_mrstft_table_floats_mel(const int *res, int n_res, int 
 extern "C" int stito_mrstft_target_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *y_dev, int rows,
                                        int64_t n_samples, float *table_dev, void *stream) {
     STITO_TRY(mr_bank_check("stito_mrstft_target_mel", bank, res, n_res));
-    return mr_target<false, true>("stito_mrstft_target_mel", res, n_res, y_dev, rows, n_samples, table_dev, stream, bank);
+    return mr_target_call("stito_mrstft_target_mel", 2, false, bank, nullptr, 0, res, n_res, y_dev, rows, n_samples, table_dev, stream);
 }
 
 extern "C" int stito_mrstft_loss_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *audio_dev, const float *peaks_dev,
                                      int norm_passes, const float *table_dev, int n_targets, int pop, int channels, int64_t n_samples,
                                      float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    STITO_TRY(mr_bank_check("stito_mrstft_loss_mel", bank, res, n_res));
-    return mr_loss<false, true>("stito_mrstft_loss_mel", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr,
-                                n_targets, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank);
+    return mr_loss_call("stito_mrstft_loss_mel", 2, false, false, bank, nullptr, 0, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev,
+                        n_targets, nullptr, 0, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int stito_mrstft_loss_slots_mel(const int *res, int n_res, const stito_mel_bank *bank, const float *audio_dev,
                                            const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
                                            const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples,
                                            float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    STITO_TRY(mr_bank_check("stito_mrstft_loss_slots_mel", bank, res, n_res));
-    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "stito_mrstft_loss_slots_mel: null target_slot_dev");
-    return mr_loss<false, true>("stito_mrstft_loss_slots_mel", res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets,
-                                target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank);
+    return mr_loss_call("stito_mrstft_loss_slots_mel", 2, false, true, bank, nullptr, 0, res, n_res, audio_dev, peaks_dev, norm_passes,
+                        table_dev, n_targets, target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
-// The prefiltered variants (ABI 10.9): one trio for the three kinds -- 0 the L/R distance, 1 sum / difference, 2 mel (with its bank)
-// -- of rows that the loader filters with n_taps taps.  The table does not record the taps: table and loss calls take the same.
-static int mr_pf_check(const char *who, int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res) {
-    STITO_REQUIRE(kind >= 0 && kind <= 2, STITO_E_INVALID, "%s: kind %d is none of 0 (L/R), 1 (sum / difference), 2 (mel)", who, kind);
-    STITO_REQUIRE(n_taps >= 1 && n_taps <= MR_PF_MAX_TAPS, STITO_E_INVALID, "%s: n_taps %d, 1 .. %d are supported", who, n_taps, MR_PF_MAX_TAPS);
-    STITO_REQUIRE((n_taps & 1) == 1, STITO_E_INVALID, "%s: n_taps %d must be odd (the filter is centred on tap n_taps / 2)", who, n_taps);
-    STITO_REQUIRE(taps_dev != nullptr, STITO_E_INVALID, "%s: null taps_dev", who);
-    if (kind == 2) return mr_bank_check(who, bank, res, n_res);
-    STITO_REQUIRE(bank == nullptr, STITO_E_INVALID, "%s: kind %d takes no bank", who, kind);
-    return STITO_OK;
-}
-
+// The prefiltered variants (ABI 10.9): one trio for the three kinds of rows that the loader filters with n_taps taps.
 static bool mr_pf_sizes_ok(int kind, int n_bins, int n_taps) {
-    if (kind < 0 || kind > 2 || n_taps < 1 || n_taps > MR_PF_MAX_TAPS || (n_taps & 1) == 0) return false;
+    if (kind < 0 || kind > 2 || n_taps < 1 || n_taps > AD_MAX_TAPS || (n_taps & 1) == 0) return false;
     return kind == 2 ? (n_bins >= 1 && n_bins <= 256) : n_bins == 0;
 }
 
@@ -839,45 +817,22 @@ extern "C" int stito_mrstft_target_pf(int kind, const stito_mel_bank *bank, cons
     if (kind == 1) STITO_TRY(mr_sd_channels(who, channels));
     STITO_REQUIRE(n_targets >= 1 && channels >= 1 && (int64_t)n_targets * channels < (1 << 30), STITO_E_INVALID, "%s: %d targets of %d channels",
                   who, n_targets, channels);
-    const int rows = n_targets * channels;
-    if (kind == 1) return mr_target<true, false, true>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, nullptr, taps_dev, n_taps);
-    if (kind == 2) return mr_target<false, true, true>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, bank, taps_dev, n_taps);
-    return mr_target<false, false, true>(who, res, n_res, y_dev, rows, n_samples, table_dev, stream, nullptr, taps_dev, n_taps);
-}
-
-static int mr_loss_pf(const char *who, int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
-                      const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
-                      const int32_t *target_slot_dev, int n_slots, int pop, int channels, int64_t n_samples, float *loss_dev,
-                      void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (kind == 1)
-        return mr_loss<true, false, true>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots, pop,
-                                          channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, nullptr, taps_dev, n_taps);
-    if (kind == 2)
-        return mr_loss<false, true, true>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots, pop,
-                                          channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, bank, taps_dev, n_taps);
-    return mr_loss<false, false, true>(who, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev, n_slots, pop,
-                                       channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream, nullptr, taps_dev, n_taps);
+    return mr_target_call(who, kind, true, bank, taps_dev, n_taps, res, n_res, y_dev, n_targets * channels, n_samples, table_dev, stream);
 }
 
 extern "C" int stito_mrstft_loss_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
                                     const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev, int n_targets,
                                     int pop, int channels, int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes,
                                     void *stream) {
-    const char *who = "stito_mrstft_loss_pf";
-    STITO_TRY(mr_pf_check(who, kind, bank, taps_dev, n_taps, res, n_res));
-    if (kind == 1) STITO_TRY(mr_sd_channels(who, channels));
-    return mr_loss_pf(who, kind, bank, taps_dev, n_taps, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, nullptr, n_targets,
-                      pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss_call("stito_mrstft_loss_pf", kind, true, false, bank, taps_dev, n_taps, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev,
+                        n_targets, nullptr, 0, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int stito_mrstft_loss_slots_pf(int kind, const stito_mel_bank *bank, const float *taps_dev, int n_taps, const int *res, int n_res,
                                           const float *audio_dev, const float *peaks_dev, int norm_passes, const float *table_dev,
                                           int n_targets, const int32_t *target_slot_dev, int n_slots, int pop, int channels,
                                           int64_t n_samples, float *loss_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    const char *who = "stito_mrstft_loss_slots_pf";
-    STITO_TRY(mr_pf_check(who, kind, bank, taps_dev, n_taps, res, n_res));
-    if (kind == 1) STITO_TRY(mr_sd_channels(who, channels));
-    STITO_REQUIRE(target_slot_dev != nullptr, STITO_E_INVALID, "%s: null target_slot_dev", who);
-    return mr_loss_pf(who, kind, bank, taps_dev, n_taps, res, n_res, audio_dev, peaks_dev, norm_passes, table_dev, n_targets, target_slot_dev,
-                      n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
+    return mr_loss_call("stito_mrstft_loss_slots_pf", kind, true, true, bank, taps_dev, n_taps, res, n_res, audio_dev, peaks_dev, norm_passes,
+                        table_dev, n_targets, target_slot_dev, n_slots, pop, channels, n_samples, loss_dev, workspace_dev, workspace_bytes, stream);
 }
+

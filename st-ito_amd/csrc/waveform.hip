@@ -20,28 +20,27 @@
 // of nothing else.  Without a prefilter the runs come straight from global memory (16-byte loads where the row is aligned and the
 // run whole, else sample by sample: the same values either way).  With one, the workgroup stages the raw run it needs in LDS -- the
 // tile and c samples on either side, zero outside the row, scaled -- and every thread filters its runs from a sliding register
-// window the way mr_prefiltered_span does: the chain of each output is fmaf in tap order from 0.0f, the taps come through scalar
-// loads.  The file is built without fp contraction and the target's table is written by the same function (template TARGET), so
-// the filtered target and a filtered candidate of the same audio have the same bits: esr, dc and logcosh of y against table(y) are
-// exactly 0.
+// window (ad_fir_run of audio_distance.h, shared with mrstft.hip like the slot rule, the folded peak, the tile tree and the host
+// checks of a loss call): the chain of each output is fmaf in tap order from 0.0f, the taps come through scalar loads.  The file is
+// built without fp contraction and the target's table is written by the same function (template TARGET), so the filtered target
+// and a filtered candidate of the same audio have the same bits: esr, dc and logcosh of y against table(y) are exactly 0.
 //
 // Sums: per lane in float64 (the products of two float32 are exact there), per tile a fixed tree in LDS, per-tile partials to the
 // workspace, and a second launch that adds a row's tiles in order, forms the requested kind from the moments in float64 and takes
 // the mean over the rows.  No atomics: a candidate's bits depend on its own audio, its peak, its target and the taps only.  The
 // log-cosh term is evaluated in float64 (coshf rounds 1 + d^2 / 2 away for small d), and only when that kind is asked for.
-#include "common.h"
+#include "audio_distance.h"
 
 namespace stito {
 
 static constexpr int WF_THREADS = 256;
 static constexpr int WF_GROUPS = 8;                          // runs of four samples per thread
 static constexpr int WF_TILE = 4 * WF_GROUPS * WF_THREADS;   // 8192 samples
-static constexpr int WF_MAX_TAPS = 255, WF_REACH = 256;      // the raw run: the tile and whole tap blocks behind it
 static constexpr int WF_MAX_CH = 8;
 static constexpr int WF_MOMENTS = 6;                         // sum d^2, d, p_x, p_x^2, p_x p_y, log-cosh term
 static constexpr int WF_KINDS = 5;                           // esr, dc, snr, sisdr, logcosh
 
-static bool wf_taps_ok(int n_taps) { return n_taps == 0 || (n_taps >= 1 && n_taps <= WF_MAX_TAPS && (n_taps & 1) == 1); }
+static bool wf_taps_ok(int n_taps) { return n_taps == 0 || (n_taps >= 1 && n_taps <= AD_MAX_TAPS && (n_taps & 1) == 1); }
 static bool wf_n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 40); }
 static int64_t wf_tiles(int64_t n) { return (n + WF_TILE - 1) / WF_TILE; }
 static int64_t wf_row_floats(int64_t n) { return (n + 3) & ~(int64_t)3; }   // rows of the table start on 16 bytes
@@ -50,13 +49,6 @@ static int64_t wf_row_floats(int64_t n) { return (n + 3) & ~(int64_t)3; }   // r
 // rows x tiles x 2 per-tile partials of those (scratch of stito_waveform_target).
 static int64_t wf_table_floats(int64_t rows, int64_t n) { return rows * wf_row_floats(n) + 4 * rows + 4 * rows * wf_tiles(n); }
 
-// As mr_target_of: population k = cand / per_target reads target slots[k], or target k without a slot list; -1: no such target.
-__device__ __forceinline__ int wf_target_of(int64_t cand, int per_target, const int32_t *__restrict__ slots, int n_targets) {
-    const int k = (int)(cand / per_target);
-    const int t = slots != nullptr ? slots[k] : k;
-    return (t >= 0 && t < n_targets) ? t : -1;
-}
-
 // ln(cosh d + eps) in float64 as log1p(2 sinh^2(d / 2) + eps), which does not round cosh d - 1 away against the 1; 0 for d == 0
 // (see the head of the file)
 __device__ __forceinline__ double wf_logcosh(double d) {
@@ -64,37 +56,8 @@ __device__ __forceinline__ double wf_logcosh(double d) {
     return d == 0.0 ? 0.0 : log1p(fma(2.0 * s, s, 1e-8));
 }
 
-// Outputs 4 g .. 4 g + 3 of the tile from the staged raw run (raw[j] = row[t0 - c + j]): p[t0 + o] = sum_k taps[k] raw[o + k].
-__device__ __forceinline__ float4 wf_filter_run(const float *raw, int g, const float *__restrict__ taps, int n_taps) {
-    // the taps are the same for every lane and nobody writes them: through the constant address space they are scalar loads
-    typedef const __attribute__((address_space(4))) float *ctaps_t;
-    ctaps_t ctaps = (ctaps_t)(uintptr_t)taps;
-    const int kb_full = n_taps >> 2, tail = n_taps & 3;           // n_taps is odd: 1 or 3 taps behind the whole blocks
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    const float4 *rp = (const float4 *)raw + g;
-    float4 lo = rp[0];
-    for (int kb = 0; kb < kb_full; ++kb) {
-        const float4 hi = rp[kb + 1];
-        const float4 t = make_float4(ctaps[4 * kb], ctaps[4 * kb + 1], ctaps[4 * kb + 2], ctaps[4 * kb + 3]);
-        a0 = fmaf(t.x, lo.x, a0); a1 = fmaf(t.x, lo.y, a1); a2 = fmaf(t.x, lo.z, a2); a3 = fmaf(t.x, lo.w, a3);
-        a0 = fmaf(t.y, lo.y, a0); a1 = fmaf(t.y, lo.z, a1); a2 = fmaf(t.y, lo.w, a2); a3 = fmaf(t.y, hi.x, a3);
-        a0 = fmaf(t.z, lo.z, a0); a1 = fmaf(t.z, lo.w, a1); a2 = fmaf(t.z, hi.x, a2); a3 = fmaf(t.z, hi.y, a3);
-        a0 = fmaf(t.w, lo.w, a0); a1 = fmaf(t.w, hi.x, a1); a2 = fmaf(t.w, hi.y, a2); a3 = fmaf(t.w, hi.z, a3);
-        lo = hi;
-    }
-    const float4 hi = rp[kb_full + 1];
-    const float t0 = ctaps[4 * kb_full];                          // no read behind the last tap
-    a0 = fmaf(t0, lo.x, a0); a1 = fmaf(t0, lo.y, a1); a2 = fmaf(t0, lo.z, a2); a3 = fmaf(t0, lo.w, a3);
-    if (tail == 3) {
-        const float t1 = ctaps[4 * kb_full + 1], t2 = ctaps[4 * kb_full + 2];
-        a0 = fmaf(t1, lo.y, a0); a1 = fmaf(t1, lo.z, a1); a2 = fmaf(t1, lo.w, a2); a3 = fmaf(t1, hi.x, a3);
-        a0 = fmaf(t2, lo.z, a0); a1 = fmaf(t2, lo.w, a1); a2 = fmaf(t2, hi.x, a2); a3 = fmaf(t2, hi.y, a3);
-    }
-    return make_float4(a0, a1, a2, a3);
-}
-
 // TARGET: audio = y (rows, n); writes the filtered rows to the table and the tile's sum p_y, sum p_y^2 (2 partials).
-// else:   audio = candidates (pop, C, n); row = cand * C + ch against table row wf_target_of(cand) * C + ch; the tile's WF_MOMENTS
+// else:   audio = candidates (pop, C, n); row = cand * C + ch against table row ad_target_of(cand) * C + ch; the tile's WF_MOMENTS
 //         partials.  A candidate whose slot names no target reads nothing and writes nothing: k_waveform_final gives it NaN.
 // PRE:    the rows go through the taps.  LC: the log-cosh term is evaluated (else its partial is 0 and nobody reads it).
 template <bool TARGET, bool PRE, bool LC>
@@ -103,7 +66,7 @@ __global__ __launch_bounds__(WF_THREADS) void k_waveform(const float *__restrict
                                                         int64_t row_floats, int64_t n, int tiles, int C, int per_target,
                                                         const int32_t *__restrict__ slots, int n_targets, double *__restrict__ partial) {
     constexpr int K = TARGET ? 2 : WF_MOMENTS;
-    __shared__ __attribute__((aligned(16))) float raw[PRE ? WF_TILE + WF_REACH : 4];
+    __shared__ __attribute__((aligned(16))) float raw[PRE ? WF_TILE + AD_TAP_REACH : 4];
     __shared__ double red[K][WF_THREADS];
 
     const int tid = threadIdx.x;
@@ -116,9 +79,9 @@ __global__ __launch_bounds__(WF_THREADS) void k_waveform(const float *__restrict
     int64_t trow = row;
     if (!TARGET) {
         const int64_t cand = row / C;
-        const int t = wf_target_of(cand, per_target, slots, n_targets);
+        const int t = ad_target_of(cand, per_target, slots, n_targets);
         if (t < 0) return;  // the whole workgroup (one row, one candidate), before it loads anything
-        if (peaks != nullptr && norm_passes > 0) r1 = 1.0f / fmaxf(peaks[cand], 1e-8f);  // x * (1 / d), as stito_logmel
+        r1 = ad_peak_scale(peaks, norm_passes, cand);
         trow = (int64_t)t * C + (row - cand * C);
     }
     const float *x = audio + row * n;
@@ -126,7 +89,7 @@ __global__ __launch_bounds__(WF_THREADS) void k_waveform(const float *__restrict
 
     if constexpr (PRE) {
         const int c = n_taps >> 1;
-        const int raw_len = ((len + 3) & ~3) + 4 * ((n_taps + 3) >> 2);   // <= WF_TILE + WF_REACH
+        const int raw_len = ((len + 3) & ~3) + 4 * ((n_taps + 3) >> 2);   // <= WF_TILE + AD_TAP_REACH
         for (int i = tid; i < raw_len; i += WF_THREADS) {
             const int64_t s = t0 - c + i;
             raw[i] = (s >= 0 && s < n) ? x[s] * r1 : 0.0f;
@@ -145,7 +108,8 @@ __global__ __launch_bounds__(WF_THREADS) void k_waveform(const float *__restrict
         if (valid <= 0) continue;
         float px[4];
         if constexpr (PRE) {
-            const float4 v = wf_filter_run(raw, g, taps, n_taps);
+            // outputs 4 g .. 4 g + 3 of the tile: raw[j] = row[t0 - c + j], so p[t0 + o] = sum_k taps[k] raw[o + k]
+            const float4 v = ad_fir_run(raw, g, taps, n_taps);
             px[0] = v.x; px[1] = v.y; px[2] = v.z; px[3] = v.w;
         } else if (x_aligned && valid == 4) {
             const float4 v = *(const float4 *)(x + t0 + 4 * g);
@@ -184,17 +148,7 @@ __global__ __launch_bounds__(WF_THREADS) void k_waveform(const float *__restrict
         }
     }
 
-    // the tile's sums: a fixed tree over the threads
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k][tid] = acc[k];
-    __syncthreads();
-    for (int s = WF_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][tid] += red[k][tid + s];
-        }
-        __syncthreads();
-    }
+    ad_tile_tree<K, WF_THREADS>(red, acc, tid);
     if (tid < K) partial[(row * tiles + tile) * K + tid] = red[tid][0];
 }
 
@@ -235,7 +189,7 @@ __global__ __launch_bounds__(64) void k_waveform_final(int kind, const double *_
                                                        int n_targets, float *__restrict__ loss) {
     __shared__ double term[WF_MAX_CH];
     const int cand = blockIdx.x, lane = threadIdx.x;
-    const int tgt = wf_target_of(cand, per_target, slots, n_targets);
+    const int tgt = ad_target_of(cand, per_target, slots, n_targets);
     if (tgt < 0) {  // the whole wave: no partial was written for this candidate and none is read
         if (lane == 0) loss[cand] = __builtin_nanf("");
         return;
@@ -260,15 +214,6 @@ __global__ __launch_bounds__(64) void k_waveform_final(int kind, const double *_
     }
 }
 
-static int wf_taps_check(const char *who, const float *taps_dev, int n_taps) {
-    STITO_REQUIRE(n_taps >= 0 && n_taps <= WF_MAX_TAPS, STITO_E_INVALID, "%s: n_taps %d, 0 (no prefilter) .. %d are supported", who, n_taps,
-                  WF_MAX_TAPS);
-    STITO_REQUIRE(n_taps == 0 || (n_taps & 1) == 1, STITO_E_INVALID, "%s: n_taps %d must be odd (the filter is centred on tap n_taps / 2)", who,
-                  n_taps);
-    STITO_REQUIRE(n_taps == 0 || taps_dev != nullptr, STITO_E_INVALID, "%s: null taps_dev", who);
-    return STITO_OK;
-}
-
 template <bool TARGET, bool LC>
 static void wf_launch(bool pre, unsigned grid, hipStream_t st, const float *audio, const float *peaks, int norm_passes, const float *taps,
                       int n_taps, float *table, int64_t n, int tiles, int C, int per_target, const int32_t *slots, int n_targets,
@@ -289,23 +234,17 @@ static int wf_loss(const char *who, int kind, const float *taps_dev, int n_taps,
     hipStream_t st = (hipStream_t)stream;
     STITO_REQUIRE(kind >= 0 && kind < WF_KINDS, STITO_E_INVALID, "%s: kind %d is none of 0 (esr), 1 (dc), 2 (snr), 3 (sisdr), 4 (logcosh)", who,
                   kind);
-    STITO_TRY(wf_taps_check(who, taps_dev, n_taps));
+    STITO_TRY(ad_taps_check(who, taps_dev, n_taps, true));
     STITO_REQUIRE(wf_n_ok(n), STITO_E_INVALID, "%s: %lld samples", who, (long long)n);
-    STITO_REQUIRE(pop >= 1 && n_targets >= 1, STITO_E_INVALID, "%s: pop %d, n_targets %d", who, pop, n_targets);
-    STITO_REQUIRE(n_slots >= 1, STITO_E_INVALID, "%s: %d target slots", who, n_slots);
-    STITO_REQUIRE(pop % n_slots == 0, STITO_E_INVALID, "%s: population %d is not a multiple of the number of targets %d", who, pop, n_slots);
-    STITO_REQUIRE(channels >= 1 && channels <= WF_MAX_CH, STITO_E_INVALID, "Invalid number of channels: %d", channels);
-    STITO_REQUIRE(norm_passes == 0 || norm_passes == 1, STITO_E_INVALID, "%s: norm_passes %d must be 0 or 1", who, norm_passes);
-    STITO_REQUIRE(norm_passes == 0 || peaks_dev != nullptr, STITO_E_INVALID, "%s: norm_passes 1 needs the peaks", who);
-    STITO_REQUIRE(audio_dev != nullptr && table_dev != nullptr && loss_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);
-    STITO_REQUIRE(((uintptr_t)table_dev & 15) == 0, STITO_E_INVALID, "%s: the table must be 16-byte aligned", who);
+    STITO_TRY(ad_loss_args_check(who, pop, n_targets, n_slots, [&] {
+        STITO_REQUIRE(channels >= 1 && channels <= WF_MAX_CH, STITO_E_INVALID, "Invalid number of channels: %d", channels);
+        return STITO_OK;
+    }, norm_passes, peaks_dev, audio_dev, table_dev, loss_dev));
     STITO_REQUIRE(((uintptr_t)audio_dev & 3) == 0, STITO_E_INVALID, "%s: the audio must be 4-byte aligned", who);
     const int64_t rows = (int64_t)pop * channels, trows = (int64_t)n_targets * channels, tiles = wf_tiles(n);
     STITO_REQUIRE(rows * tiles < ((int64_t)1 << 31), STITO_E_UNSUPPORTED, "%s: too many tiles", who);
     const size_t need = (size_t)rows * tiles * WF_MOMENTS * sizeof(double);
-    STITO_REQUIRE(workspace_dev != nullptr && workspace_bytes >= need, STITO_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
-                  workspace_bytes, need);
-    STITO_REQUIRE(((uintptr_t)workspace_dev & 7) == 0, STITO_E_INVALID, "%s: the workspace must be 8-byte aligned", who);
+    STITO_TRY(ad_workspace_check(who, workspace_dev, workspace_bytes, need));
     double *partial = (double *)workspace_dev;
     const double *ysum = (const double *)(table_dev + trows * wf_row_floats(n));
     const unsigned grid = (unsigned)(rows * tiles);
@@ -343,7 +282,7 @@ extern "C" int stito_waveform_target(const float *taps_dev, int n_taps, const fl
                                      void *stream) {
     const char *who = "stito_waveform_target";
     hipStream_t st = (hipStream_t)stream;
-    STITO_TRY(wf_taps_check(who, taps_dev, n_taps));
+    STITO_TRY(ad_taps_check(who, taps_dev, n_taps, true));
     STITO_REQUIRE(wf_n_ok(n_samples), STITO_E_INVALID, "%s: %lld samples", who, (long long)n_samples);
     STITO_REQUIRE(rows >= 1, STITO_E_INVALID, "%s: %d rows", who, rows);
     STITO_REQUIRE(y_dev != nullptr && table_dev != nullptr, STITO_E_INVALID, "%s: null pointer", who);

@@ -782,6 +782,13 @@ class MrstftEvaluator(_Evaluator):
 
     _loss_options = {}  # what a subclass's tables take in `loss` beyond the above (WaveformEvaluator: its kind)
 
+    def _uploaded_taps(self):
+        """The prefilter taps of a subclass that has some (self.taps, host float32, or None) on the device: uploaded once, at the
+        first table, and shared by all the evaluator's tables."""
+        if self.taps is not None and self._taps_dev is None:
+            self._taps_dev = torch.from_numpy(self.taps).to(self.device)
+        return self._taps_dev
+
 
 class MelMrstftEvaluator(MrstftEvaluator):
     """MrstftEvaluator with the mel-scaled distance (features.MelMrstftTarget; auraloss's scale="mel"): every table holds band sums
@@ -830,10 +837,8 @@ class PrefilteredMrstftEvaluator(MrstftEvaluator):
     def _target_table(self, y: torch.Tensor):
         from . import features as _features
 
-        if self._taps_dev is None:
-            self._taps_dev = torch.from_numpy(self.taps).to(self.device)
         return _features.PrefilteredMrstftTarget(y, self.taps, kind=self.kind, resolutions=self.resolutions, bank=self._bank,
-                                                 taps_dev=self._taps_dev)
+                                                 taps_dev=self._uploaded_taps())
 
 
 class WaveformEvaluator(MrstftEvaluator):
@@ -860,6 +865,4 @@ class WaveformEvaluator(MrstftEvaluator):
     def _target_table(self, y: torch.Tensor):
         from . import features as _features
 
-        if self.taps is not None and self._taps_dev is None:
-            self._taps_dev = torch.from_numpy(self.taps).to(self.device)
-        return _features.WaveformTarget(y, self.taps, taps_dev=self._taps_dev)
+        return _features.WaveformTarget(y, self.taps, taps_dev=self._uploaded_taps())

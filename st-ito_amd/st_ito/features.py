@@ -7,6 +7,7 @@ the host exactly like the reference does (pyloudnorm there, st_ito.loudness here
 """
 from __future__ import annotations
 
+import functools
 import math
 import warnings
 
@@ -286,11 +287,74 @@ def _mrstft_stereo(stereo, channels) -> bool:
     return stereo == "sum-diff"
 
 
-class MrstftTarget:
+class _TargetTable:
+    """What the target tables of the audio distances (MR-STFT, waveform) share: the shape of y (T, C, n), a device table that
+    `update` refills for another y of that shape, and the scaffolding of `loss`.  A kind of table states its hooks: `_name` (of
+    the table in messages, of its scratch in a Workspace), `_table_floats()`, `_workspace_bytes(pop)`, `_fill(y)` -- the call
+    that writes the table -- and `_loss_calls(...)` -> (the plain loss call, the one with a slot list), functools.partials that
+    already carry every argument in front of audio_dev."""
+
+    def __init__(self, y: torch.Tensor):
+        self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
+        floats = self._table_floats()
+        if floats <= 0:
+            raise ValueError(f"no {self._name} table for {tuple(y.shape)} audio")
+        self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
+        self.update(y)
+
+    def update(self, y: torch.Tensor):
+        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
+        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
+            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
+        self._fill(y.contiguous())
+        return self
+
+    def _taps_ptr(self):
+        """The table's prefilter taps (self.taps, host float32, or None) on its device -> their pointer, or None: uploaded at the
+        first call, unless the constructor was handed a tensor that already holds them (self._taps_dev)."""
+        if self.taps is None:
+            return None
+        if self._taps_dev is None:
+            self._taps_dev = torch.from_numpy(self.taps).to(self.table.device)
+        assert self._taps_dev.is_cuda and self._taps_dev.dtype == torch.float32 and self._taps_dev.numel() == self.taps.size
+        return _hip.ptr(self._taps_dev)
+
+    def _loss(self, audio: torch.Tensor, peaks, norm_passes: int, slots, ws, *head) -> torch.Tensor:
+        """`loss` of every kind of table; head: what the kind's `_loss_calls` takes."""
+        if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
+            raise ValueError(f"audio must be (P, {self.channels}, {self.n}), got {tuple(audio.shape)}")
+        assert audio.is_cuda and audio.dtype == torch.float32
+        audio = audio.contiguous()
+        P = audio.shape[0]
+        ws = _hip.scratch(self._workspace_bytes(P), audio.device, ws, self._name.lower())
+        out = torch.empty(P, dtype=torch.float32, device=audio.device)
+        plain, with_slots = self._loss_calls(*head)
+        front = (_hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table), self.n_targets)
+        back = (P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr())
+        if slots is None:
+            _hip.check(plain(*front, *back))
+            return out
+        if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
+            raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
+        _hip.check(with_slots(*front, _hip.ptr(slots), slots.numel(), *back))
+        return out
+
+
+def _check_pair(x: torch.Tensor, y: torch.Tensor) -> None:
+    """The shapes every compute_*_distance takes: estimate x (B, C, n), reference y (B, C, n) or (1, C, n)."""
+    if x.dim() != 3 or y.dim() != 3:
+        raise ValueError("expected (bs, chs, seq_len)")
+    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+
+
+class MrstftTarget(_TargetTable):
     """The target side of the distance on the device: the table stito_mrstft_target writes for y (T, C, n) -- FFT tables,
     clamped magnitudes per (row, resolution), sum |Y|^2 -- in a buffer that `update` refills for another y of the same shape.
     stereo="sum-diff": the rows of a target are its L + R and L - R (stito_mrstft_target_sd) and `loss` forms the same two rows of
     every candidate in its loader -- auraloss's SumAndDifferenceSTFTLoss with both weights 1; 2-channel audio only."""
+
+    _name = "MRSTFT"
 
     def __init__(self, y: torch.Tensor, resolutions=None, stereo: str = "lr"):
         self.res, self.n_res = _mrstft_res(resolutions)
@@ -299,15 +363,9 @@ class MrstftTarget:
         self.sum_diff = _mrstft_stereo(stereo, y.shape[1])
         _mrstft_check_length(y.shape[-1], resolutions)
         self.resolutions = resolutions
-        self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
-        floats = self._table_floats()
-        if floats <= 0:
-            raise ValueError(f"no MRSTFT table for {tuple(y.shape)} audio")
-        self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
-        self.update(y)
+        super().__init__(y)
 
-    # The places where the kinds of table differ (MelMrstftTarget and PrefilteredMrstftTarget override them): the table's size, the
-    # call that fills it, the two loss entry points with what they take between n_res and the audio, and the workspace's size.
+    # _TargetTable's hooks; MelMrstftTarget and PrefilteredMrstftTarget override them
     def _table_floats(self) -> int:
         return _hip.lib().stito_mrstft_table_floats(self.res, self.n_res, self.n_targets * self.channels, self.n)
 
@@ -324,18 +382,9 @@ class MrstftTarget:
                                              _hip.ptr(self.table), _hip.stream_ptr()))
 
     def _loss_calls(self):
-        """-> (the plain call, the call with a slot list, the arguments both take between n_res and audio_dev)"""
         L = _hip.lib()
-        if self.sum_diff:
-            return L.stito_mrstft_loss_sd, L.stito_mrstft_loss_slots_sd, ()
-        return L.stito_mrstft_loss, L.stito_mrstft_loss_slots, ()
-
-    def update(self, y: torch.Tensor) -> "MrstftTarget":
-        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
-        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
-            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
-        self._fill(y.contiguous())
-        return self
+        calls = (L.stito_mrstft_loss_sd, L.stito_mrstft_loss_slots_sd) if self.sum_diff else (L.stito_mrstft_loss, L.stito_mrstft_loss_slots)
+        return tuple(functools.partial(c, self.res, self.n_res) for c in calls)
 
     def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None, ws=None) -> torch.Tensor:
         """audio (P, C, n) float32 on the GPU, P a multiple of the number of targets (candidate p against target p // (P // T))
@@ -344,25 +393,7 @@ class MrstftTarget:
         the table (stito_mrstft_loss_slots: any subset, any order; a slot that names no target gives NaN).  A sum / difference
         table goes through the _sd entry points, same arguments.  ws: the evaluator's engine.Workspace the kernels' scratch comes
         from (None: allocated for this call on the current stream)."""
-        if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
-            raise ValueError(f"audio must be (P, {self.channels}, {self.n}), got {tuple(audio.shape)}")
-        assert audio.is_cuda and audio.dtype == torch.float32
-        audio = audio.contiguous()
-        P = audio.shape[0]
-        L = _hip.lib()
-        ws = _hip.scratch(self._workspace_bytes(P), audio.device, ws, "mrstft")
-        out = torch.empty(P, dtype=torch.float32, device=audio.device)
-        plain, with_slots, between = self._loss_calls()
-        if slots is None:
-            _hip.check(plain(self.res, self.n_res, *between, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
-                             self.n_targets, P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
-            return out
-        if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
-            raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
-        _hip.check(with_slots(self.res, self.n_res, *between, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table),
-                              self.n_targets, _hip.ptr(slots), slots.numel(), P, self.channels, self.n, _hip.ptr(out),
-                              _hip.ptr(ws), ws.numel(), _hip.stream_ptr()))
-        return out
+        return self._loss(audio, peaks, norm_passes, slots, ws)
 
 
 def compute_mrstft_distance(x: torch.Tensor, y: torch.Tensor, resolutions=None) -> torch.Tensor:
@@ -381,10 +412,7 @@ def compute_sd_mrstft_distance(x: torch.Tensor, y: torch.Tensor, resolutions=Non
 
 
 def _mrstft_distance(x, y, resolutions, stereo):
-    if x.dim() != 3 or y.dim() != 3:
-        raise ValueError("expected (bs, chs, seq_len)")
-    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
-        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _check_pair(x, y)
     _mrstft_stereo(stereo, x.shape[1])
     _mrstft_res(resolutions)
     _mrstft_check_length(x.shape[-1], resolutions)
@@ -490,8 +518,8 @@ class MelMrstftTarget(MrstftTarget):
                                                       self.n_targets * self.channels, self.n, _hip.ptr(self.table), _hip.stream_ptr()))
 
     def _loss_calls(self):
-        L = _hip.lib()
-        return L.stito_mrstft_loss_mel, L.stito_mrstft_loss_slots_mel, (self._device_bank().ref,)
+        L, bank = _hip.lib(), self._device_bank().ref
+        return tuple(functools.partial(c, self.res, self.n_res, bank) for c in (L.stito_mrstft_loss_mel, L.stito_mrstft_loss_slots_mel))
 
 
 def compute_mel_mrstft_distance(x: torch.Tensor, y: torch.Tensor, sample_rate, n_bins: int = MEL_MRSTFT_BINS,
@@ -500,10 +528,7 @@ def compute_mel_mrstft_distance(x: torch.Tensor, y: torch.Tensor, sample_rate, n
     unpinned) -> (B,) float32 on x's device, with compute_mrstft_distance's shape rules: the magnitudes of every frame are summed
     into n_bins Slaney mel bands before the spectral convergence and the log-magnitude term are taken, so the near-silent bins
     above a few kHz no longer carry the loss.  ValueError, before anything touches the GPU, for a bank with an empty band."""
-    if x.dim() != 3 or y.dim() != 3:
-        raise ValueError("expected (bs, chs, seq_len)")
-    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
-        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _check_pair(x, y)
     bank = mel_mrstft_bank(sample_rate, n_bins, resolutions)
     _mrstft_check_length(x.shape[-1], resolutions)
     xin, dev = _gpu(x)
@@ -593,16 +618,12 @@ class PrefilteredMrstftTarget(MrstftTarget):
 
     def _head(self):
         """(kind, bank or None, taps_dev, n_taps): what every prefiltered call takes first."""
-        dev = self.table.device
-        if self._taps_dev is None:
-            self._taps_dev = torch.from_numpy(self.taps).to(dev)
-        assert self._taps_dev.is_cuda and self._taps_dev.dtype == torch.float32 and self._taps_dev.numel() == self.taps.size
         bank = None
         if self.kind == "mel":
             if self._bank is None:
-                self._bank = _DeviceMelBank(self._host_bank, dev)
+                self._bank = _DeviceMelBank(self._host_bank, self.table.device)
             bank = self._bank.ref
-        return _PREFILTER_KINDS[self.kind], bank, _hip.ptr(self._taps_dev), int(self.taps.size)
+        return _PREFILTER_KINDS[self.kind], bank, self._taps_ptr(), int(self.taps.size)
 
     def _table_floats(self) -> int:
         return _hip.lib().stito_mrstft_table_floats_pf(_PREFILTER_KINDS[self.kind], self.n_bins, int(self.taps.size), self.res, self.n_res,
@@ -617,10 +638,8 @@ class PrefilteredMrstftTarget(MrstftTarget):
                                                      self.n, _hip.ptr(self.table), _hip.stream_ptr()))
 
     def _loss_calls(self):
-        import functools
-
         L, head = _hip.lib(), self._head()
-        return functools.partial(L.stito_mrstft_loss_pf, *head), functools.partial(L.stito_mrstft_loss_slots_pf, *head), ()
+        return tuple(functools.partial(c, *head, self.res, self.n_res) for c in (L.stito_mrstft_loss_pf, L.stito_mrstft_loss_slots_pf))
 
 
 def compute_prefiltered_mrstft_distance(x: torch.Tensor, y: torch.Tensor, prefilter, sample_rate=None, kind: str = "lr",
@@ -632,10 +651,7 @@ def compute_prefiltered_mrstft_distance(x: torch.Tensor, y: torch.Tensor, prefil
     if kind not in _PREFILTER_KINDS:
         raise ValueError(f"kind must be one of {sorted(_PREFILTER_KINDS)}, got {kind!r}")
     taps = mrstft_prefilter(prefilter, sample_rate)
-    if x.dim() != 3 or y.dim() != 3:
-        raise ValueError("expected (bs, chs, seq_len)")
-    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
-        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _check_pair(x, y)
     _mrstft_stereo("sum-diff" if kind == "sum-diff" else "lr", x.shape[1])
     bank = None
     if kind == "mel":
@@ -674,7 +690,7 @@ def _waveform_check_shape(channels: int, n: int) -> None:
         raise ValueError(f"{int(n)} samples: the waveform distances need at least 1")
 
 
-class WaveformTarget:
+class WaveformTarget(_TargetTable):
     """The target side of the waveform distances on the device, the shape of MrstftTarget: the table stito_waveform_target writes for
     y (T, C, n) -- the rows after the prefilter (a copy of y without one) and their float64 sums -- in a buffer that `update` refills
     for another y of the same shape.  prefilter: None, or mrstft_prefilter's argument ("aw" needs sample_rate): target and
@@ -683,58 +699,36 @@ class WaveformTarget:
     SISDRLoss, LogCoshLoss, restated, parity unpinned; the formulas stand in include/stito_hip.h).  taps_dev: a device tensor that
     already holds exactly these taps (an evaluator's)."""
 
+    _name = "waveform"
+
     def __init__(self, y: torch.Tensor, prefilter=None, sample_rate=None, taps_dev=None):
         self.taps = _waveform_taps(prefilter, sample_rate)
         self.n_taps = 0 if self.taps is None else int(self.taps.size)
         if y.dim() != 3:
             raise ValueError("expected (n_targets, chs, seq_len)")
         _waveform_check_shape(y.shape[1], y.shape[2])
-        self.n_targets, self.channels, self.n = (int(v) for v in y.shape)
         self._taps_dev = taps_dev
-        floats = _hip.lib().stito_waveform_table_floats(self.n_taps, self.n_targets * self.channels, self.n)
-        if floats <= 0:
-            raise ValueError(f"no waveform table for {tuple(y.shape)} audio")
-        self.table = torch.empty(floats, dtype=torch.float32, device=y.device)
-        self.update(y)
+        super().__init__(y)
 
-    def _taps_ptr(self):
-        if self.taps is None:
-            return None
-        if self._taps_dev is None:
-            self._taps_dev = torch.from_numpy(self.taps).to(self.table.device)
-        assert self._taps_dev.is_cuda and self._taps_dev.dtype == torch.float32 and self._taps_dev.numel() == self.n_taps
-        return _hip.ptr(self._taps_dev)
+    def _table_floats(self) -> int:
+        return _hip.lib().stito_waveform_table_floats(self.n_taps, self.n_targets * self.channels, self.n)
 
-    def update(self, y: torch.Tensor) -> "WaveformTarget":
-        """One launch sequence on the current stream: the table of y (same shape as at construction, float32, on the table's GPU)."""
-        if tuple(y.shape) != (self.n_targets, self.channels, self.n) or not y.is_cuda or y.dtype != torch.float32:
-            raise ValueError(f"target audio must be a float32 GPU tensor of shape {(self.n_targets, self.channels, self.n)}")
-        _hip.check(_hip.lib().stito_waveform_target(self._taps_ptr(), self.n_taps, _hip.ptr(y.contiguous()), self.n_targets * self.channels,
-                                                    self.n, _hip.ptr(self.table), _hip.stream_ptr()))
-        return self
+    def _workspace_bytes(self, pop: int) -> int:
+        return _hip.lib().stito_waveform_workspace_bytes(self.n_taps, pop, self.channels, self.n)
+
+    def _fill(self, y: torch.Tensor) -> None:
+        _hip.check(_hip.lib().stito_waveform_target(self._taps_ptr(), self.n_taps, _hip.ptr(y), self.n_targets * self.channels, self.n,
+                                                    _hip.ptr(self.table), _hip.stream_ptr()))
+
+    def _loss_calls(self, kind: int):
+        L, taps = _hip.lib(), self._taps_ptr()
+        return tuple(functools.partial(c, kind, taps, self.n_taps) for c in (L.stito_waveform_loss, L.stito_waveform_loss_slots))
 
     def loss(self, audio: torch.Tensor, peaks=None, norm_passes: int = 0, slots=None, ws=None, kind: str = "esr") -> torch.Tensor:
         """audio (P, C, n) float32 on the GPU -> (P,) float32, candidate p against target p // (P // T); peaks / norm_passes / slots /
         ws: as MrstftTarget.loss (the folded peak normalisation, the slot list of stito_waveform_loss_slots, the evaluator's
         engine.Workspace).  kind: "esr", "dc", "snr", "sisdr" or "logcosh"."""
-        k = _waveform_kind(kind)
-        if audio.dim() != 3 or tuple(audio.shape[1:]) != (self.channels, self.n):
-            raise ValueError(f"audio must be (P, {self.channels}, {self.n}), got {tuple(audio.shape)}")
-        assert audio.is_cuda and audio.dtype == torch.float32
-        audio = audio.contiguous()
-        P = audio.shape[0]
-        L = _hip.lib()
-        ws = _hip.scratch(L.stito_waveform_workspace_bytes(self.n_taps, P, self.channels, self.n), audio.device, ws, "waveform")
-        out = torch.empty(P, dtype=torch.float32, device=audio.device)
-        head = (k, self._taps_ptr(), self.n_taps, _hip.ptr(audio), _hip.ptr(peaks), int(norm_passes), _hip.ptr(self.table), self.n_targets)
-        tail = (P, self.channels, self.n, _hip.ptr(out), _hip.ptr(ws), ws.numel(), _hip.stream_ptr())
-        if slots is None:
-            _hip.check(L.stito_waveform_loss(*head, *tail))
-            return out
-        if not (slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()):
-            raise ValueError("slots must be a contiguous 1-D int32 tensor on the GPU")
-        _hip.check(L.stito_waveform_loss_slots(*head, _hip.ptr(slots), slots.numel(), *tail))
-        return out
+        return self._loss(audio, peaks, norm_passes, slots, ws, _waveform_kind(kind))
 
 
 def compute_waveform_distance(x: torch.Tensor, y: torch.Tensor, kind: str = "esr", prefilter=None, sample_rate=None) -> torch.Tensor:
@@ -744,10 +738,7 @@ def compute_waveform_distance(x: torch.Tensor, y: torch.Tensor, kind: str = "esr
     filter); "aw" needs sample_rate.  Every ValueError -- the kind, the taps, the shapes -- comes before anything touches the GPU."""
     _waveform_kind(kind)
     taps = _waveform_taps(prefilter, sample_rate)
-    if x.dim() != 3 or y.dim() != 3:
-        raise ValueError("expected (bs, chs, seq_len)")
-    if y.shape[0] not in (1, x.shape[0]) or tuple(y.shape[1:]) != tuple(x.shape[1:]):
-        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} do not match (y may have batch 1)")
+    _check_pair(x, y)
     _waveform_check_shape(x.shape[1], x.shape[2])
     xin, dev = _gpu(x)
     yin = y.detach().to(dev, torch.float32).contiguous()

@@ -9,9 +9,6 @@ one process, medians of --reps calls after warm-up, for the linear and for the m
       (101 taps - 1 tap) is the filter's fmas and LDS reads and (1 tap - plain) the loader's extra passes.
 --trace runs only the four loss calls, --reps times each, for a `rocprofv3 --kernel-trace --stats -- python
 tools/mrstft_aw_bench.py --trace` run of its own: k_mrstft<false, false, MEL, true> are the prefiltered kernels.
---dump FILE writes the losses of the six unfiltered instantiations (the L/R, sum / difference and mel calls, table and candidate
-kernels) on the inputs of tests/mrstft_cases.py and tests/mrstft_sd_cases.py as an .npz and stops: run once with STITO_LIB_PATH at
-a library of the parent revision (tools/build_rev_lib.sh) and once without, then --compare A B says whether they are bit-identical.
     python tools/mrstft_aw_bench.py [--pop 256] [--reps 20] [--out profiles/mrstft_aw.txt]"""
 import argparse
 import contextlib
@@ -50,52 +47,15 @@ def alternating_ms(fns, reps, wall=False):
     return [(statistics.median(v), min(v), max(v)) for v in out]
 
 
-def dump(path):
-    """The unfiltered calls' losses on the test inputs, every float32 as it comes.  Works with a library that predates the
-    prefiltered symbols."""
-    from st_ito import _hip
-    if os.environ.get("STITO_LIB_PATH"):
-        for name in [k for k in _hip.SIGNATURES if k.endswith("_pf")]:
-            del _hip.SIGNATURES[name]
-    import mrstft_cases as M
-    import mrstft_sd_cases as SDC
-    from st_ito.features import MelMrstftTarget, MrstftTarget
-    dev = torch.device("cuda", 0)
-    out = {}
-    for form, cases in (("lr", M.cases()), ("sd", SDC.cases()), ("mel", M.cases())):
-        for name, x, y, norm_passes in cases:
-            xd, yd = M.scored(x, norm_passes).to(dev).contiguous(), y.to(dev).contiguous()
-            tgt = MelMrstftTarget(yd, 48000) if form == "mel" else MrstftTarget(yd, None, "sum-diff" if form == "sd" else "lr")
-            out[f"{form}/{name}"] = tgt.loss(xd).cpu().numpy()
-            out[f"{form}/{name}/table"] = tgt.table.cpu().numpy()[: tgt.table.numel() // 2]     # FFT tables and magnitudes
-    np.savez(path, **out)
-    print(f"{path}: {len(out)} arrays, library {_hip.LIB_PATH}")
-
-
-def compare(a, b):
-    A, B = np.load(a), np.load(b)
-    assert sorted(A.files) == sorted(B.files)
-    bad = [k for k in A.files if A[k].tobytes() != B[k].tobytes()]
-    print(f"{len(A.files)} arrays (losses and table halves of the six unfiltered instantiations over the test inputs): "
-          + ("bit-identical" if not bad else f"{len(bad)} DIFFER: {bad[:8]}"))
-    return not bad
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pop", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--n", type=int, default=262144)
     ap.add_argument("--trace", action="store_true", help="only the loss kernels, for a kernel trace")
-    ap.add_argument("--dump", default=None)
-    ap.add_argument("--compare", nargs=2, default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.compare:
-        sys.exit(0 if compare(*a.compare) else 1)
     assert torch.cuda.is_available(), "needs a GPU: there is nothing to time without one"
-    if a.dump:
-        return dump(a.dump)
     import eval_pst
     from st_ito import _hip, engine
     from st_ito.features import MelMrstftTarget, MrstftTarget, PrefilteredMrstftTarget, mel_mrstft_bank
